@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — headline metric of BASELINE.json on MI355X.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
          bench.py --gpus N --steps K --warmup W
 
@@ -10,6 +10,11 @@ hierarchical loss + backward + Adam step (train.py:245-268) on 32 synthetic 64^3
 occupancy PER GPU (BASELINE.json configs[1]; weak scaling: N GPUs process N*32 independent blocks, the
 only exchange is one flat fp32 gradient all-reduce over RCCL).  Inputs are resident in HBM before the timed
 region.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up (including the untimed --settle steps), W warm-up steps, the K timed
+steps, --dump-outputs if given, the JSON line.  --full adds everything else the result line can carry, measured after the
+timed region: the roofline leg, the rocprofv3 PMC passes, the comparison legs and the CPU baseline (the --no-* switches
+below turn single ones off again).
 
 This file holds the driver's contract: argument parsing, the process group, the timed headline leg and the JSON line.
 The measurement legs around it live in benchlib/: cpu_leg.py (cpu_baseline), roofline.py (HIP-event roofline accounting),
@@ -45,6 +50,11 @@ def parse():
     ap.add_argument('--batch', type=int, default=32, help='blocks per GPU')
     ap.add_argument('--dim', type=int, default=64)
     ap.add_argument('--occupancy', type=float, default=0.05)
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline: roofline leg, PMC passes, comparison legs and CPU baseline (default: headline only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default='',
+                    help='write what the last timed step computed to DIR/<name>.npy (float32): its loss, its per-level losses and '
+                         'the parameters + BatchNorm buffers it left behind')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-baseline-only', action='store_true', help='internal: run the CPU leg alone, print its JSON')
     ap.add_argument('--cpu-torch-only', action='store_true',
@@ -71,8 +81,8 @@ def parse():
                          '+1 %% per step until they reach the data\'s own occupancy after ~250 steps, scripts/diag_drift.py); '
                          'the timed region should see that converged workload, not a point on the transient')
     ap.add_argument('--no-prefetch', action='store_true', help='classic teacher-forced steps build their own geometry')
-    ap.add_argument('--no-other-mode', action='store_true', help='skip the comparison legs (profiling runs)')
-    ap.add_argument('--no-traffic', action='store_true', help='skip the rocprofv3 --pmc passes (roofline.traffic, counters_in_step)')
+    ap.add_argument('--no-other-mode', action='store_true', help='--full: skip the comparison legs (profiling runs)')
+    ap.add_argument('--no-traffic', action='store_true', help='--full: skip the rocprofv3 --pmc passes (roofline.traffic, counters_in_step)')
     ap.add_argument('--traffic-probe', action='store_true', help='internal: the isolated PMC probe (run under rocprofv3 --pmc)')
     return ap.parse_args()
 
@@ -106,6 +116,18 @@ def cpu_child(args):
         except (OSError, ValueError):
             pass
     print(json.dumps(cpu_leg.cpu_baseline(args)))
+
+
+def dump_outputs(path, loss, losses, model):
+    """--dump-outputs: what the last timed step handed its caller (the loss, the per-level losses; -1 where a level has no
+    loss) and what it left behind (every parameter and BatchNorm buffer of the model after its update, state_dict order,
+    flattened), float32, one .npy file each (~2.6 MB at the default model size)."""
+    os.makedirs(path, exist_ok=True)
+    value = lambda v: float(v.detach()) if torch.is_tensor(v) else float(v)
+    state = [v.detach().float().reshape(-1).cpu() for v in model.state_dict().values() if v.is_floating_point()]
+    np.save(os.path.join(path, 'loss.npy'), np.array([value(loss)], dtype=np.float32))
+    np.save(os.path.join(path, 'level_losses.npy'), np.array([value(v) for v in (losses or [])], dtype=np.float32))
+    np.save(os.path.join(path, 'model_state.npy'), torch.cat(state).numpy().astype(np.float32))
 
 
 def main():
@@ -221,6 +243,8 @@ def main():
         replays0 = gs.stats['replays']
         torch.cuda.reset_peak_memory_stats(dev)
         elapsed = timed(step, args.warmup, args.steps)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, gs.loss, gs.losses, model)
         graph_info = dict(gs.stats)
         # device memory of the replayed steps: `reserved` is what the process holds (the graph's private pool — every
         # intermediate of the captured step — static buffers, parameters / Adam state, workspaces); `allocated` counts only
@@ -238,24 +262,25 @@ def main():
         row_map = RL.capacity_row_map(graph_info['capacity'], live)
         from benchlib.legs import live_sites
         levels = live_sites(args, live)
-        # roofline leg: the same capacity-mode steps issued eagerly (same kernels, same sizes) with HIP events around
-        # every convolution launch — events cannot sit inside a replayed graph
-        gs._drain()
-        gs.stage, gs.use_graph = 2, False
-        launches0 = lib.sgnn_launch_count()
-        step(0)
-        torch.cuda.synchronize()
-        graph_info['library_launches_per_step'] = int(lib.sgnn_launch_count() - launches0)
-        lib.sgnn_prof_enable(1 << 15)
-        for i in range(4):
-            step(i)
-            n_prof_steps += 1
-        torch.cuda.synchronize()
-        lib.sgnn_prof_disable()
-        valid = RL.measure_valid_ratios(step, 0)
-        timing_note = ('HIP events around every convolution launch of %d capacity-mode steps issued eagerly right after the '
-                       'timed region (same kernels and sizes as the replayed graph; events cannot be recorded inside a replay)'
-                       % n_prof_steps)
+        if args.full:
+            # roofline leg: the same capacity-mode steps issued eagerly (same kernels, same sizes) with HIP events around
+            # every convolution launch — events cannot sit inside a replayed graph
+            gs._drain()
+            gs.stage, gs.use_graph = 2, False
+            launches0 = lib.sgnn_launch_count()
+            step(0)
+            torch.cuda.synchronize()
+            graph_info['library_launches_per_step'] = int(lib.sgnn_launch_count() - launches0)
+            lib.sgnn_prof_enable(1 << 15)
+            for i in range(4):
+                step(i)
+                n_prof_steps += 1
+            torch.cuda.synchronize()
+            lib.sgnn_prof_disable()
+            valid = RL.measure_valid_ratios(step, 0)
+            timing_note = ('HIP events around every convolution launch of %d capacity-mode steps issued eagerly right after '
+                           'the timed region (same kernels and sizes as the replayed graph; events cannot be recorded inside a '
+                           'replay)' % n_prof_steps)
     else:
         P_.PERSISTENT_ARENAS = True          # grow-only program arenas (a training loop never keeps two forward results)
         model = make_model()
@@ -266,8 +291,9 @@ def main():
         def step(i):
             return train_step(model, opt, batches[i % 2], lw, grad_sync=sync, teacher_forced=teacher, prefetch=pre,
                               next_batch=batches[(i + 1) % 2] if pre is not None else None)
-        lib.sgnn_prof_enable(1 << 15)
-        lib.sgnn_prof_disable()
+        if args.full:
+            lib.sgnn_prof_enable(1 << 15)
+            lib.sgnn_prof_disable()
         holder, outs_box = {}, {}
 
         def hook(i, before):   # HIP events around every conv launch of every 4th timed step
@@ -280,17 +306,20 @@ def main():
                 holder['n'] = holder.get('n', 0) + 1
 
         def step_keep(i):
-            outs_box['o'] = step(i)[2]
-        elapsed = timed(step_keep, args.warmup, args.steps, hook)
+            outs_box['r'] = step(i)
+        elapsed = timed(step_keep, args.warmup, args.steps, hook if args.full else None)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, outs_box['r'][0], outs_box['r'][1], model)
         n_prof_steps = holder.get('n', 0)
         from benchlib.legs import sites
-        levels = sites(outs_box['o'])
-        valid = RL.measure_valid_ratios(step, args.warmup + args.steps)
-        timing_note = 'HIP events around every convolution launch of every 4th timed step'
+        levels = sites(outs_box['r'][2])
+        if args.full:
+            valid = RL.measure_valid_ratios(step, args.warmup + args.steps)
+            timing_note = 'HIP events around every convolution launch of every 4th timed step'
 
     # ---- comparison legs, same process, same box ---------------------------------------------------------------
     legs = None
-    if args.steps >= 20 and not args.no_other_mode and not share and not classic:
+    if args.full and args.steps >= 20 and not args.no_other_mode and not share and not classic:
         from benchlib.legs import comparison_legs
         P_.PERSISTENT_ARENAS = True
         gs._drain()
@@ -301,9 +330,11 @@ def main():
                                 'flat_sync': flat_sync, 'dist_on': dist_on, 'teacher': teacher})
 
     if rank == 0:
-        agg = RL.collect_prof(lib, valid, row_map if not classic else None)
-        dom_key, roof = RL.roofline_record(agg, n_prof_steps, timing_note)
         step_ms = 1e3 * elapsed / args.steps
+        roof = None
+        if args.full:
+            agg = RL.collect_prof(lib, valid, row_map if not classic else None)
+            dom_key, roof = RL.roofline_record(agg, n_prof_steps, timing_note)
         if roof is not None:
             if world == 1 and not args.no_traffic:
                 from benchlib import pmc
@@ -323,7 +354,7 @@ def main():
                               'profiled launches with live rows and rules-only flops, BatchNorm 32 N C, row movement) / '
                               'ms_per_step / peak; dense 8^3 bottleneck excluded'}
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             from benchlib import cpu_leg
             cpu = cpu_leg.cpu_baseline_subprocess(args, os.path.abspath(__file__))
         masks = ('generative masks teacher-forced from the target hierarchy (row counts independent of the weights)' if teacher

@@ -6,8 +6,8 @@ How it uses "all cores": the step's BatchNorm statistics, rulebook builds and gl
 regions, so ONE step does not scale past ~16 threads (round 3: 12.6 blocks/s at 16 threads, 1.95 at 128).  The reference
 parallelises over samples; the unit that is independent end to end here is a REPLICA — a step over its own blocks with its own
 BatchNorm statistics, exactly the partitioning the multi-GPU run uses (HISTORY.md section 6).  The all-cores figure therefore
-runs R = cores / T replicas side by side (T threads each, pinned to disjoint cores, idle OpenMP threads sleeping) and reports
-the aggregate blocks/s.  Measured on the 2 x 64-core EPYC 9575F of the GPU boxes (profiles/r04j_cpu_leg.txt): the aggregate
+runs R = budget / T replicas side by side (budget: the cores this process may use, cpu_budget(); T threads each, pinned to
+disjoint cores, idle OpenMP threads sleeping) and reports the aggregate blocks/s.  Measured on the 2 x 64-core EPYC 9575F of the GPU boxes (profiles/r04j_cpu_leg.txt): the aggregate
 saturates at ~20 blocks/s from 8 replicas on (4 x 32 threads 16.0, 8 x 16: 18.5, 16 x 8: 19.9, 32 x 4: 20.1) while every
 replica slows down 5-8x — the oracle's step is bound by the host's memory system (gathers over 92 k-row levels from 128
 cores), not by core count; T = 8 is the default."""
@@ -42,6 +42,26 @@ def cpu_info():
     except OSError:
         pass
     return model, (len(cores) or (os.cpu_count() or 1))
+
+
+def cpu_budget(phys):
+    """CPUs the CPU leg may occupy: the physical cores, bounded by this process's affinity mask, a cgroup CPU quota and an
+    OMP_NUM_THREADS set by the caller, where present.  A host shared through a CPU quota shows all of its cores in
+    os.cpu_count() and /proc/cpuinfo; sizing the replicas by those would put many times more threads on the quota than
+    it has CPUs (and start one replica process per 8 cores of the whole host)."""
+    n = phys
+    if hasattr(os, 'sched_getaffinity'):
+        n = min(n, len(os.sched_getaffinity(0)))
+    try:
+        quota, period = open('/sys/fs/cgroup/cpu.max').read().split()[:2]
+        if quota != 'max':
+            n = min(n, max(1, int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    omp = os.environ.get('OMP_NUM_THREADS', '')
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, n)
 
 
 def cpu_baseline(args):
@@ -123,14 +143,15 @@ def _result(p, timeout=900):
 
 def cpu_baseline_subprocess(args, bench_path):
     """The CPU leg in its own processes (the GPU process is pinned to its GPU's NUMA node and OpenMP pools are sized at
-    start-up): one replica on 1 thread and on T = min(16, cores) threads, then R = cores // T replicas side by side on
-    disjoint cores — the all-cores figure and the headline."""
+    start-up): one replica on 1 thread and on T = min(8, budget) threads, then R = budget // T replicas side by side on
+    disjoint cores — the all-cores figure and the headline.  budget = cpu_budget(): the cores this process may use."""
     model, phys = cpu_info()
     ncpu = os.cpu_count() or phys
-    T = min(int(os.environ.get('SGNN_CPU_LEG_THREADS', '8')), phys)       # threads per replica
-    R = max(1, phys // T)
+    budget = cpu_budget(phys)
+    T = min(int(os.environ.get('SGNN_CPU_LEG_THREADS', '8')), budget)     # threads per replica
+    R = max(1, budget // T)
     res = {}
-    legs = [('one_thread', 1), ('one_replica_%d_threads' % T, T)] + ([('one_replica_16_threads', 16)] if phys >= 32 and T != 16 else [])
+    legs = [('one_thread', 1), ('one_replica_%d_threads' % T, T)] + ([('one_replica_16_threads', 16)] if budget >= 32 and T != 16 else [])
     for tag, nt in legs:
         if tag == 'one_thread' and os.environ.get('SGNN_CPU_LEG_SKIP_ONE') == '1':
             continue
@@ -168,5 +189,6 @@ def cpu_baseline_subprocess(args, bench_path):
         by[k] = {'threads': v.get('threads', v.get('cores')), 'value': round(v['value'], 4), 's_per_step': v['s_per_step']}
         if 'replicas' in v:
             by[k]['replicas'] = v['replicas']
-    cpu.update({'cpu_model': model, 'physical_cores': phys, 'threads_of_headline': cpu['cores'], 'by_threads': by})
+    cpu.update({'cpu_model': model, 'physical_cores': phys, 'cpu_budget': budget, 'threads_of_headline': cpu['cores'],
+                'by_threads': by})
     return cpu

@@ -1,6 +1,6 @@
 """GPU: device marching cubes + mesh clean-up against the REFERENCE's own compiled extension — stored outputs
-(tests/golden/mc_expected.npz, made with oracle/_ref/marching_cubes_cpp.so) and, where that prebuilt module
-travelled with the snapshot, live runs of it at scene size.  Everything is compared bit for bit."""
+(tests/golden/mc_expected.npz, made with oracle/_ref/marching_cubes_cpp.so) and, at scene size, stored sizes + digests
+of its meshes (tests/golden/live_reference.npz).  Everything is compared bit for bit."""
 import os
 import sys
 
@@ -20,15 +20,6 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope='module')
 def g():
     return np.load(os.path.join(HERE, 'golden', 'mc_expected.npz'))
-
-
-def ref_module():
-    sys.path.insert(0, os.path.join(os.path.dirname(HERE), 'oracle', '_ref'))
-    try:
-        import marching_cubes_cpp
-        return marching_cubes_cpp
-    except ImportError:
-        return None
 
 
 def same_mesh(got, want):
@@ -72,21 +63,17 @@ def test_host_tensor_rejected_by_the_kernel_entry():
 
 
 def test_scene_size_against_live_reference():
-    """(96,160,192) surface volume: ~1e5 triangles, long welding chains along shared edges."""
-    ref = ref_module()
-    if ref is None:
-        pytest.skip('oracle/_ref/marching_cubes_cpp.so not present (built by __graft_entry__.build() where the '
-                    'reference sources exist)')
-    spec = dict(dims=(96, 160, 192), seed=11, occ=0.12, iso=0.0, trunc=3.0, thresh=10.0, kind='block')
-    tsdf, _ = make_volume(spec)
-    col = torch.ones(tuple(tsdf.shape) + (3,), dtype=torch.uint8) * 220
-    want = [t.numpy() for t in ref.run_marching_cubes(tsdf, col, 0.0, 3.0, 10.0)]
-    assert len(want[2]) > 20000
-    same_mesh(mc.run_marching_cubes(tsdf.cuda(), None, 0.0, 3.0, 10.0), want)
-    noisy = dict(spec, kind='quantised', seed=12)
-    tsdf, _ = make_volume(noisy)
-    want = [t.numpy() for t in ref.run_marching_cubes(tsdf, col, 0.0, 3.0, 10.0)]
-    same_mesh(mc.run_marching_cubes(tsdf.cuda(), None, 0.0, 3.0, 10.0), want)
+    """(96,160,192) surface volume: ~1e5 triangles, long welding chains along shared edges.  The reference extension's
+    meshes of these volumes are stored as sizes + sha256 digests (tests/golden/live_reference.npz,
+    tests/golden/make_golden_live.py): bit for bit, like every other comparison here."""
+    import live_cases
+    g = live_cases.load()
+    vols, _ = live_cases.mc_scene_volumes()
+    for i, tsdf in enumerate(vols):
+        v, c, f = (t.cpu().numpy() for t in mc.run_marching_cubes(tsdf.cuda(), None, 0.0, 3.0, 10.0))
+        assert [len(v), len(f)] == g['mcscene%d_shapes' % i].tolist(), (i, len(v), len(f))
+        assert len(f) > 20000 and c.dtype == np.uint8 and f.dtype == np.int32
+        assert live_cases.digest(v, c, f) == str(g['mcscene%d_sha' % i]), 'scene-size mesh %d differs from the reference' % i
 
 
 def test_save_predictions_files_match_reference(g, tmp_path):

@@ -120,49 +120,17 @@ def test_writer_reader_round_trip(tmp_path):
 
 @pytest.mark.parametrize('seed', range(4))
 def test_readers_match_live_reference_on_random_files(tmp_path, seed):
-    """Random chunk / scene files decoded by the reference's own data_util.py (imported live where /root/reference
-    exists; plyfile / marching_cubes stubbed as in tests/golden/make_golden_data.py), the oracle and the host loader."""
-    ref_dir = '/root/reference/torch'
-    if not os.path.isdir(ref_dir):
-        pytest.skip('reference sources not present on this machine')
-    import types
-    # stubs only for the duration of the import (other tests import the REAL marching_cubes_cpp of oracle/_ref)
-    added = []
-    for name in ('plyfile', 'marching_cubes', 'marching_cubes.marching_cubes'):
-        if name not in sys.modules:
-            sys.modules[name] = types.ModuleType(name)
-            added.append(name)
-    sys.modules['marching_cubes'].marching_cubes = sys.modules['marching_cubes.marching_cubes']
-    sys.path.insert(0, ref_dir)
-    try:
-        import data_util as ref_data
-    finally:
-        sys.path.remove(ref_dir)
-        for name in added:
-            sys.modules.pop(name, None)
-    from sgnn_amd import synth
-    rng = np.random.default_rng(seed)
-    dims = tuple(int(8 * v) for v in rng.integers(1, 4, 3))
-    vs = float(rng.choice([0.02, 0.046875, 0.1]))
-    p = str(tmp_path / 'c.sdfs')
-    synth.write_chunk(p, dims, 40 + seed, occupancy=float(rng.uniform(0.05, 0.4)), voxelsize=vs)
-    want = ref_data.load_train_file(p)
+    """Random chunk / scene files decoded by the reference's own data_util.py (its outputs on these very files are stored
+    in tests/golden/live_reference.npz by tests/golden/make_golden_live.py), the oracle and the host loader."""
+    import live_cases
+    g = live_cases.load()
+    chunk, s_tgt, knw = live_cases.data_files(str(tmp_path), seed)
+    assert live_cases.file_digest(chunk) == str(g['data%d_chunk_sha' % seed])       # the files the reference decoded
+    assert live_cases.file_digest(s_tgt) == str(g['data%d_scene_sha' % seed])
     for mod in (data_oracle, data):
-        got = mod.load_train_file(p)
-        same(got[0][0], want[0][0])
-        same(got[0][1], want[0][1])
-        same(got[1], want[1])
-        assert list(got[2]) == list(want[2])
-        same(got[3], want[3])
-        same(got[4], want[4])
-        for h in range(3):
-            same(got[5][h], want[5][h])
-    s_in, s_tgt = str(tmp_path / 'a.sdf'), str(tmp_path / 'b.sdf')
-    synth.write_scene_triple(s_in, s_tgt, (int(rng.integers(9, 30)), int(rng.integers(9, 30)), int(rng.integers(9, 30))),
-                             60 + seed, occupancy=0.3, voxelsize=vs)
-    for mod in (data_oracle, data):
-        got, want = mod.load_scene(s_tgt), ref_data.load_scene(s_tgt)
-        same(got[0][0], want[0][0])
-        same(got[0][1], want[0][1])
-        assert list(got[1]) == list(want[1])
-        same(mod.load_scene_known(s_tgt[:-4] + '.knw'), ref_data.load_scene_known(s_tgt[:-4] + '.knw'))
+        got = live_cases.train_fields(mod.load_train_file(chunk))
+        for k, v in got.items():
+            same(v, g['data%d_train_%s' % (seed, k)])
+        got = live_cases.scene_fields(mod.load_scene(s_tgt), mod.load_scene_known(knw))
+        for k, v in got.items():
+            same(v, g['data%d_scene_%s' % (seed, k)])

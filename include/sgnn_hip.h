@@ -561,13 +561,18 @@ int sgnn_loss_levels_bwd(const int64_t *levels, int n, const float *coef_host, c
  * mode 1: floats of the arena sgnn_prog_forward needs (buffers + per-op areas);
  * mode 2: the same for an INFERENCE call (sgnn_prog_forward with training = 2): no backward pass may follow, so a
  *         buffer's storage is reused once its last reader has run — the arena is the high-water mark of the live set,
- *         3-4x smaller for a U-Net stage (whole-scene inference, BASELINE configs[3]). */
+ *         3-4x smaller for a U-Net stage (whole-scene inference, BASELINE configs[3]);
+ * mode 3: the same with bf16 storage (sgnn_prog_forward with training = 2 | 4).  Still counted in floats: a buffer of
+ *         n rows takes ceil(n * ld / 2) floats, ld = its channels rounded up to a multiple of 8 bf16 elements; LINEAR
+ *         outputs stay fp32 (ld = channels).  sgnn_prog_buffer_offset: infer = 2 gives this layout's offsets. */
 int64_t sgnn_prog_arena_floats(const int32_t *ops, int nops, const int32_t *bufs, int nbuf, int n_ext,
                                const int64_t *lev_n, int nlev, const int32_t *keep, int mode);
 int64_t sgnn_prog_ws_bytes(const int32_t *ops, int nops, const int64_t *lev_n, int nlev);
 int64_t sgnn_prog_buffer_offset(const int32_t *ops, int nops, const int32_t *bufs, int nbuf, int n_ext,
                                 const int64_t *lev_n, int nlev, const int32_t *keep, int infer, int b);
-/* training: 0 = eval, 1 = training (batch statistics), | 2 = inference layout (see sgnn_prog_arena_floats mode 2).
+/* training: 0 = eval, 1 = training (batch statistics), | 2 = inference layout (see sgnn_prog_arena_floats mode 2),
+ * | 4 = bf16 storage (mode 3; only as 2 | 4, eval: running statistics).  In the bf16 layout the externals stay fp32,
+ * every arena buffer is bf16 except the LINEAR outputs (fp32 logits); math is fp32 with one rounding per stored value.
  * wait_event (hipEvent_t or NULL): the stream waits for it right before the program's first Convolution(2,2) — the
  * first operation that touches the stride-2 tables and the coarser levels' hash / rulebook / row counts, which the caller
  * may have built on another stream (they then overlap the level-0 operations in front of it). */
@@ -598,6 +603,44 @@ int sgnn_prog_set_side_stream(sgnn_stream_t stream2, void *ws2, int64_t ws2_byte
  * gradient — its first, widest convolution — otherwise holds up the next program's dependent chain for as long as it runs.
  * Returns the previous setting. */
 int sgnn_prog_defer_join(int on);
+/* ---------------------------------------------------------------------------
+ * bf16 inference kernels (infer_bf16.hip; what sgnn_prog_forward runs with training = 2 | 4).  bf16 rows are uint16
+ * bit patterns with a row stride ld* in ELEMENTS; fp32 math, one round-to-nearest-even per stored value.  Readers of
+ * 16-byte row chunks (the convolutions) zero the channels >= cin in registers: pad columns may hold anything.
+ * sgnn_bf16_conv_fwd: the rulebook walk of sgnn_conv_fwd (K = 27 submanifold / 8 stride-2, offset-major table, ld a
+ *   multiple of 256) over bf16 rows with v_mfma_f32_16x16x32_bf16 (cin, cout <= 64; other widths: a plain generic
+ *   kernel); fp32 weights (K, cin, cout) are rounded to bf16 into ws (sgnn_bf16_conv_ws_bytes(cin, cout, K, 0) bytes);
+ *   optional bf16 residual `addend` added before the rounding; n_dev: capacity mode (rows past *n_dev untouched).
+ *   ldx must be even and x dword-aligned.
+ * sgnn_bf16_conv_expand: the 8-child up-sampling convolution (sgnn_conv_fwd_ex on the parent rulebook: child row
+ *   8p + parity), from the 3x3x3 weights w; ws: sgnn_bf16_conv_ws_bytes(cin, cout, 27, 1) bytes.
+ * sgnn_bf16_bn_eval: y = act((x - running_mean) / sqrt(running_var + eps) * gamma + beta), act = leaky ReLU (leak).
+ * sgnn_bf16_gather_rows: y[r] = x[idx[r]] (UnPooling); sgnn_bf16_add: y = a + b; sgnn_bf16_join: y = [a | b].
+ * sgnn_bf16_concat3: fp32 sources (contiguous, optional row indices, -1 = zeros) -> bf16 rows [a | b | c].
+ * sgnn_bf16_linear: bf16 rows -> fp32 logits y[n][cout] (cout <= 4; w: cout x cin, bias: cout or NULL).
+ * sgnn_bf16_to_f32: bf16 rows (stride ldx) -> contiguous fp32 [n][c].
+ * ------------------------------------------------------------------------- */
+int64_t sgnn_bf16_conv_ws_bytes(int cin, int cout, int K, int expand);
+int sgnn_bf16_conv_fwd(const void *x, int64_t n_in, int cin, int64_t ldx, const float *w, int K, const int32_t *table,
+                       int64_t ld, int64_t n_out, int cout, void *y, int64_t ldy, const void *addend, int64_t ld_add,
+                       const int64_t *n_dev, void *ws, int64_t ws_bytes, sgnn_stream_t stream);
+int sgnn_bf16_conv_expand(const void *x, int64_t n, int cin, int64_t ldx, const float *w, const int32_t *nbr, int64_t ld,
+                          int cout, void *y, int64_t ldy, const int64_t *n_dev, void *ws, int64_t ws_bytes,
+                          sgnn_stream_t stream);
+int sgnn_bf16_bn_eval(const void *x, int64_t ldx, int64_t n, int c, const float *gamma, const float *beta,
+                      const float *running_mean, const float *running_var, float eps, float leak, void *y, int64_t ldy,
+                      const int64_t *n_dev, sgnn_stream_t stream);
+int sgnn_bf16_gather_rows(const void *x, int64_t ldx, int c, const int32_t *idx, int64_t m, void *y, int64_t ldy,
+                          const int64_t *n_dev, sgnn_stream_t stream);
+int sgnn_bf16_add(const void *a, int64_t lda, const void *b, int64_t ldb, int64_t n, int c, void *y, int64_t ldy,
+                  const int64_t *n_dev, sgnn_stream_t stream);
+int sgnn_bf16_join(const void *a, int64_t lda, int ca, const void *b, int64_t ldb, int cb, int64_t n, void *y, int64_t ldy,
+                   const int64_t *n_dev, sgnn_stream_t stream);
+int sgnn_bf16_concat3(const float *a, int ca, const int32_t *ia, const float *b, int cb, const int32_t *ib, const float *c,
+                      int cc, const int32_t *ic, int64_t m, void *y, int64_t ldy, const int64_t *n_dev, sgnn_stream_t stream);
+int sgnn_bf16_linear(const void *x, int64_t ldx, int64_t n, int cin, const float *w, const float *bias, int cout, float *y,
+                     const int64_t *n_dev, sgnn_stream_t stream);
+int sgnn_bf16_to_f32(const void *x, int64_t ldx, int64_t n, int c, float *y, const int64_t *n_dev, sgnn_stream_t stream);
 /* ---------------------------------------------------------------------------
  * Optimizer step (torch/train.py:81 optim.Adam, :264 optimizer.step()) as one launch over flat buffers of all n
  * parameters.  seg: HOST array of nseg (<= 8) x 5 int64 = {begin, end, cnt, flag, step}: elements [begin, end) are

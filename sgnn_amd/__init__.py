@@ -10,3 +10,12 @@ Package contents (only what the hot path of SURVEY.md §8 needs):
   synth.py     synthetic TSDF blocks in the layout scene_dataloader.collate emits
 """
 __version__ = '0.1.0'
+
+
+def __getattr__(name):
+    # sgnn_amd.bf16_inference: the bf16 inference mode of the program executor (scn/program.py); resolved lazily so that
+    # importing the package stays free of torch / the native library
+    if name == 'bf16_inference':
+        from .scn.program import bf16_inference
+        return bf16_inference
+    raise AttributeError(name)

@@ -102,6 +102,18 @@ PROTOTYPES = {
     'sgnn_prog_buffer_offset': (c_i64, [c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32]),
     'sgnn_prog_set_side_stream': (c_i32, [c_vp, c_vp, c_i64]),
     'sgnn_prog_defer_join': (c_i32, [c_i32]),
+    'sgnn_bf16_conv_ws_bytes': (c_i64, [c_i32, c_i32, c_i32, c_i32]),
+    'sgnn_bf16_conv_fwd': (c_i32, [c_vp, c_i64, c_i32, c_i64, c_vp, c_i32, c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp,
+                                   c_i64, c_vp, c_vp, c_i64, c_vp]),
+    'sgnn_bf16_conv_expand': (c_i32, [c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_i64,
+                                      c_vp]),
+    'sgnn_bf16_bn_eval': (c_i32, [c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_vp, c_i64, c_vp, c_vp]),
+    'sgnn_bf16_gather_rows': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    'sgnn_bf16_add': (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp]),
+    'sgnn_bf16_join': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    'sgnn_bf16_concat3': (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    'sgnn_bf16_linear': (c_i32, [c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    'sgnn_bf16_to_f32': (c_i32, [c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp]),
     'sgnn_prog_forward': (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp,
                                   c_i32, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp]),
     'sgnn_prog_backward': (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp,

@@ -25,6 +25,18 @@ enum {
 // conv.hip entry points without a prototype in the public header
 extern "C" int sgnn_expand_weights(const float *w, int cin, int cout, float *wc, sgnn_stream_t stream);
 extern "C" int sgnn_expand_weights_bwd(const float *dwc, int cin, int cout, float *dw, sgnn_stream_t stream);
+// infer_bf16.hip: the kernels of the bf16 inference layout
+int64_t sgnn_bf16_wfrag_bytes(int cin, int cout, int K, int groups);
+int sgnn_bf16_conv_prepare(const float *w, int cin, int cout, int K, int groups, void *wf, sgnn_stream_t stream);
+int sgnn_bf16_conv_run(const void *x, int64_t n_in, int cin, int64_t ldx, const float *w, const void *wf, int K,
+                       const int32_t *table, int64_t ld, int64_t n_out, int cout, void *y, int64_t ldy,
+                       const void *addend, int64_t ld_add, const int32_t *kmap, int groups, int table_rows,
+                       const int64_t *n_dev, sgnn_stream_t stream);
+int sgnn_bf16_conv_expand_impl(const void *x, int64_t n, int cin, int64_t ldx, const float *w, const int32_t *nbr,
+                               int64_t ld, int cout, void *y, int64_t ldy, const int64_t *n_dev, void *ws,
+                               sgnn_stream_t stream);
+int sgnn_bf16_linear_rows(const void *x, int64_t ldx, int64_t n, int cin, const float *const *w, const float *const *b,
+                          int cout, float *y, const int64_t *n_dev, sgnn_stream_t stream);
 
 namespace {
 
@@ -71,10 +83,20 @@ struct Plan {
   std::vector<int64_t> ld;       // per buffer: row stride in floats
   std::vector<char> join_view;   // per op: this JoinTable is in place
   std::vector<int> lin_bn;       // per op: a LINEAR head whose data gradient is formed inside the backward pass of BatchNorm lin_bn[i] (BnLin; -1: written)
+  bool bf16 = false;             // bf16 inference layout: ld in bf16 elements, a multiple of 8 (LINEAR outputs: fp32, ld = channels)
+  std::vector<char> f32;         // per buffer: stored as fp32 (always, except in the bf16 layout where only LINEAR outputs are)
 };
 
+inline int64_t round8(int64_t v) { return (v + 7) & ~int64_t(7); }
 
-void make_plan(const View &v, const int32_t *keep, Plan &P) {
+
+void make_plan(const View &v, const int32_t *keep, Plan &P, bool bf16 = false) {
+  P.bf16 = bf16;
+  P.f32.assign(v.nbuf, bf16 ? 0 : 1);
+  if (bf16)
+    for (int i = 0; i < v.nops; ++i)
+      if (v.ops[OPW * i] == OP_LINEAR && v.ops[OPW * i + 3] >= 0 && v.ops[OPW * i + 3] < v.nbuf) P.f32[v.ops[OPW * i + 3]] = 1;
+  auto row_ld = [&](int r) -> int64_t { return P.f32[r] ? v.bufs[2 * r + 1] : round8(v.bufs[2 * r + 1]); };
   P.add_dst.assign(v.nops, -1);
   P.skip.assign(v.nops, 0);
   P.join_view.assign(v.nops, 0);
@@ -84,7 +106,7 @@ void make_plan(const View &v, const int32_t *keep, Plan &P) {
   P.ld.resize(v.nbuf);
   for (int b = 0; b < v.nbuf; ++b) {
     P.root[b] = b;
-    P.ld[b] = v.bufs[2 * b + 1];
+    P.ld[b] = row_ld(b);
   }
   if (!g_fuse) return;
   std::vector<int> readers = count_readers(v);
@@ -152,6 +174,7 @@ void make_plan(const View &v, const int32_t *keep, Plan &P) {
            p[0] == OP_BN || p[0] == OP_UNPOOL;
     }
     if (!ok || o[1] == o[2]) continue;
+    if (bf16 && (o[6] & 1)) continue;   // bf16 rows: the second input's columns must start dword-aligned (16-byte chunk loads)
     P.join_view[i] = 1;
     P.skip[i] = 1;
     P.root[o[1]] = o[3];
@@ -167,7 +190,7 @@ void make_plan(const View &v, const int32_t *keep, Plan &P) {
     }
     P.root[b] = r;
     P.col[b] = c;
-    P.ld[b] = v.bufs[2 * r + 1];
+    P.ld[b] = row_ld(r);
   }
 }
 
@@ -177,7 +200,21 @@ void make_plan(const View &v, const int32_t *keep, Plan &P) {
 struct Layout {
   std::vector<int64_t> buf_off, buf_floats, aux_off;
   int64_t max_buf = 0, total = 0, fwd_total = 0, scratch0 = 0, scratch1 = 0, bextra = 0;
+  // bf16 layout: an external read by anything but CONCAT_IN gets a bf16 copy in the arena (shadow), converted in front of
+  // its first reader (first[b]); first[] holds the first op touching every storage root
+  std::vector<char> shadow;
+  std::vector<int> first;
 };
+
+// per-op area of the bf16 layout (floats): the convolutions' bf16 weight fragments, the up-sampling convolution's
+// pre-summed fp32 slices in front of its fragments; BatchNorm needs none (eval only: running statistics)
+int64_t aux_floats_bf16(const int32_t *o) {
+  if (o[0] == OP_CONV_SUBM || o[0] == OP_CONV_DOWN)
+    return round64(sgnn_bf16_wfrag_bytes(o[6], o[7], o[0] == OP_CONV_DOWN ? 8 : 27, 1) / 4);
+  if (o[0] == OP_EXPAND)
+    return round64(64 * (int64_t)o[6] * o[7]) + round64(sgnn_bf16_wfrag_bytes(o[6], o[7], 8, 8) / 4);
+  return 0;
+}
 
 // Inference layout (no backward pass will read the arena): a buffer's storage is handed to later buffers once its last
 // reader has run.  Storage roots are allocated at the first op that writes into them (an in-place JoinTable's inputs
@@ -187,8 +224,9 @@ struct Layout {
 int make_layout_infer(const View &v, const Plan &P, const int32_t *keep, Layout &L) {
   const int never = v.nops + 1;
   std::vector<int> first(v.nbuf, never), last(v.nbuf, -1);
+  auto in_arena = [&](int b) { return b >= v.n_ext || L.shadow[b]; };
   auto touch = [&](int b, int i) {
-    if (b < v.n_ext || b >= v.nbuf) return;
+    if (b < 0 || b >= v.nbuf || !in_arena(b)) return;
     const int r = P.root[b];
     if (i < first[r]) first[r] = i;
     if (i > last[r]) last[r] = i;
@@ -206,7 +244,13 @@ int make_layout_infer(const View &v, const Plan &P, const int32_t *keep, Layout 
   int64_t off = 0;
   for (int i = 0; i < v.nops; ++i) {   // per-op areas first: small and alive for the whole call
     const int32_t *o = v.ops + OPW * i;
-    if (o[0] == OP_BN) {
+    if (P.bf16) {
+      const int64_t a = aux_floats_bf16(o);
+      if (a > 0) {
+        L.aux_off[i] = off;
+        off += a;
+      }
+    } else if (o[0] == OP_BN) {
       L.aux_off[i] = off;
       off += round64(2 * (int64_t)o[6]);
     } else if (o[0] == OP_EXPAND) {
@@ -253,16 +297,17 @@ int make_layout_infer(const View &v, const Plan &P, const int32_t *keep, Layout 
     return o;
   };
   for (int i = 0; i < v.nops; ++i) {
-    for (int b = v.n_ext; b < v.nbuf; ++b)      // everything whose last toucher ran before this op
-      if (P.root[b] == b && L.buf_off[b] >= 0 && last[b] == i - 1) release(L.buf_off[b], round64(L.buf_floats[b]));
-    for (int b = v.n_ext; b < v.nbuf; ++b)
-      if (P.root[b] == b && first[b] == i) L.buf_off[b] = take(round64(L.buf_floats[b]));
+    for (int b = 0; b < v.nbuf; ++b)      // everything whose last toucher ran before this op
+      if (in_arena(b) && P.root[b] == b && L.buf_off[b] >= 0 && last[b] == i - 1) release(L.buf_off[b], round64(L.buf_floats[b]));
+    for (int b = 0; b < v.nbuf; ++b)
+      if (in_arena(b) && P.root[b] == b && first[b] == i) L.buf_off[b] = take(round64(L.buf_floats[b]));
   }
   for (int b = v.n_ext; b < v.nbuf; ++b) {
     if (P.root[b] == b && L.buf_off[b] < 0) L.buf_off[b] = 0;   // never touched (a fused-away convolution output)
   }
-  for (int b = v.n_ext; b < v.nbuf; ++b)
-    if (P.root[b] != b) L.buf_off[b] = L.buf_off[P.root[b]] + P.col[b];
+  for (int b = v.n_ext; b < v.nbuf; ++b)   // (bf16: col counts elements — the executor adds it in bytes, see forward_bf16)
+    if (P.root[b] != b) L.buf_off[b] = P.bf16 ? L.buf_off[P.root[b]] : L.buf_off[P.root[b]] + P.col[b];
+  L.first = first;
   L.fwd_total = L.total = top;
   L.scratch0 = L.scratch1 = L.bextra = top;
   return 0;
@@ -272,14 +317,24 @@ int make_layout(const View &v, const Plan &P, Layout &L, bool infer = false, con
   L.buf_off.assign(v.nbuf, -1);
   L.buf_floats.resize(v.nbuf);
   L.aux_off.assign(v.nops, -1);
+  L.shadow.assign(v.nbuf, 0);
   int64_t off = 0;
+  if (P.bf16 && !infer) return -1;       // bf16 storage exists in the inference layout only
   if (infer) {
     for (int b = 0; b < v.nbuf; ++b) {
       const int lev = v.bufs[2 * b], ch = v.bufs[2 * b + 1];
       if (lev < 0 || lev >= v.nlev || ch < 1) return -1;
-      L.buf_floats[b] = v.lev_n[lev] * (int64_t)(P.root[b] == b ? P.ld[b] : ch);
+      const int64_t elems = v.lev_n[lev] * (int64_t)(P.root[b] == b ? P.ld[b] : ch);
+      L.buf_floats[b] = P.f32[b] ? elems : (elems + 1) / 2;     // bf16: two elements per float of the arena
       if (L.buf_floats[b] > L.max_buf) L.max_buf = L.buf_floats[b];
     }
+    if (P.bf16)
+      for (int i = 0; i < v.nops; ++i) {
+        const int32_t *o = v.ops + OPW * i;
+        if (o[0] == OP_CONCAT_IN) continue;      // reads the fp32 externals itself
+        for (int b : {o[1], (o[0] == OP_ADD || o[0] == OP_JOIN) ? o[2] : -1})
+          if (b >= 0 && b < v.n_ext) L.shadow[b] = 1;
+      }
     return make_layout_infer(v, P, keep, L);
   }
   for (int b = 0; b < v.nbuf; ++b) {
@@ -424,14 +479,15 @@ SGNN_EXPORT int sgnn_prog_defer_join(int on) {
   } while (0)
 
 // mode 0: the gradient arena of sgnn_prog_backward (buffers + per-op areas + backward scratch); 1: the arena of
-// sgnn_prog_forward (buffers + per-op areas); 2: the forward arena of an inference call (training = 2: liveness-packed)
+// sgnn_prog_forward (buffers + per-op areas); 2: the forward arena of an inference call (training = 2: liveness-packed);
+// 3: the same with bf16 storage (training = 2 | 4)
 SGNN_EXPORT int64_t sgnn_prog_arena_floats(const int32_t *ops, int nops, const int32_t *bufs, int nbuf, int n_ext,
                                            const int64_t *lev_n, int nlev, const int32_t *keep, int mode) {
   View v{ops, nullptr, nops, bufs, nbuf, n_ext, lev_n, nullptr, nullptr, nullptr, nullptr, nullptr, nlev};
   Plan P;
-  make_plan(v, keep, P);
+  make_plan(v, keep, P, mode == 3);
   Layout L;
-  if (mode < 0 || mode > 2 || make_layout(v, P, L, mode == 2, keep) != 0) return -1;
+  if (mode < 0 || mode > 3 || make_layout(v, P, L, mode >= 2, keep) != 0) return -1;
   return mode == 0 ? L.total : L.fwd_total;
 }
 
@@ -440,15 +496,129 @@ SGNN_EXPORT int64_t sgnn_prog_ws_bytes(const int32_t *ops, int nops, const int64
   return ws_need(v);
 }
 
-// float offset of buffer `b` inside an arena (so the host layer can hand out views); -1 for externals
+// float offset of buffer `b` inside an arena (so the host layer can hand out views); -1 for externals.  infer: 0 training
+// layout, 1 inference layout, 2 bf16 inference layout (rows of round-up-to-8 bf16 elements; LINEAR outputs stay fp32)
 SGNN_EXPORT int64_t sgnn_prog_buffer_offset(const int32_t *ops, int nops, const int32_t *bufs, int nbuf, int n_ext,
                                             const int64_t *lev_n, int nlev, const int32_t *keep, int infer, int b) {
   View v{ops, nullptr, nops, bufs, nbuf, n_ext, lev_n, nullptr, nullptr, nullptr, nullptr, nullptr, nlev};
   Plan P;
-  make_plan(v, keep, P);
+  make_plan(v, keep, P, infer == 2);
   Layout L;
-  if (make_layout(v, P, L, infer != 0, keep) != 0 || b < 0 || b >= nbuf) return -1;
+  if (infer < 0 || infer > 2 || make_layout(v, P, L, infer != 0, keep) != 0 || b < 0 || b >= nbuf || b < n_ext) return -1;
   return P.root[b] == b ? L.buf_off[b] : -1;      // buffers the caller keeps are never views
+}
+
+// The forward pass of the bf16 inference layout (training = 2 | 4; infer_bf16.hip): the same plan — fused conv ->
+// AddTable, in-place JoinTable views — over bf16 rows (row strides rounded up to 8 elements).  Externals stay the
+// caller's fp32 tensors: CONCAT_IN converts while it gathers, any other reader gets a bf16 shadow copy made in front of
+// its first reader.  LINEAR heads write fp32 logits.  Eval only (running statistics).
+static int forward_bf16(const View &v, const Plan &PL, const Layout &L, void *const *ext, void *const *idx, int nidx,
+                        void *const *params, int nparams, void *const *lev_cnt, float *arena, void *wait_event,
+                        sgnn_stream_t stream) {
+  const int32_t *ops = v.ops, *bufs = v.bufs;
+  const int n_ext = v.n_ext, nbuf = v.nbuf, nlev = v.nlev;
+  // storage of buffer b: the caller's tensor, or its root's arena slot + its column offset (bf16 elements)
+  auto B = [&](int b) -> void * {
+    if (b < 0) return nullptr;
+    if (b < n_ext && !L.shadow[b]) return ext[b];
+    const int r = PL.root[b];
+    return (char *)arena + 4 * L.buf_off[r] + (PL.f32[r] ? 4 : 2) * (int64_t)PL.col[b];
+  };
+  auto LD = [&](int b) -> int64_t { return PL.ld[b]; };
+  auto CH = [&](int b) { return b < 0 ? 0 : bufs[2 * b + 1]; };
+  auto ROWS = [&](int b) { return v.lev_n[bufs[2 * b]]; };
+  auto P = [&](int p) { return (p >= 0 && p < nparams) ? (float *)params[p] : nullptr; };
+  auto I = [&](int i) { return (i >= 0 && i < nidx && idx) ? (const int32_t *)idx[i] : nullptr; };
+  auto CNT = [&](int cls) -> const int64_t * { return (lev_cnt && cls >= 0 && cls < nlev) ? (const int64_t *)lev_cnt[cls] : nullptr; };
+  auto EXT = [&](int b) -> const float * { return b < 0 ? nullptr : (const float *)ext[b]; };
+  for (int i = 0; i < v.nops; ++i) {
+    const int32_t *o = ops + OPW * i;
+    const int type = o[0], in0 = o[1], in1 = o[2], out = o[3], par = o[4], lev = o[5], cin = o[6], cout = o[7];
+    SGNN_CHECK_ARG(out >= n_ext && out < nbuf && lev >= 0 && lev < nlev && in0 < nbuf && in1 < nbuf);
+    SGNN_CHECK_ARG(type == OP_CONCAT_IN || in0 >= 0);
+    SGNN_CHECK_ARG(type == OP_LINEAR || !PL.f32[out]);
+    const int64_t n = v.lev_n[lev];
+    for (int b = 0; b < n_ext; ++b)       // bf16 copies of the externals this op is the first to read
+      if (L.shadow[b] && L.first[b] == i)
+        PROG_TRY(sgnn_bf16_concat3(EXT(b), CH(b), nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, ROWS(b), B(b), LD(b),
+                                   CNT(bufs[2 * b]), stream));
+    if (PL.skip[i]) continue;
+    if (type == OP_CONV_DOWN && wait_event) {     // (as in the fp32 layout: the pyramid lane's tables)
+      sgnn_stamp("down-wait<", stream);
+      SGNN_HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)wait_event, 0));
+      sgnn_stamp("down-wait>", stream);
+      wait_event = nullptr;
+    }
+    switch (type) {
+      case OP_CONV_SUBM:
+      case OP_CONV_DOWN: {
+        const bool down = type == OP_CONV_DOWN;
+        SGNN_CHECK_ARG(!down || lev + 1 < nlev);
+        const int K = down ? 8 : 27;
+        const int64_t n_out = down ? v.lev_n[lev + 1] : n;
+        const int32_t *table = (const int32_t *)(down ? v.lev_children[lev] : v.lev_nbr[lev]);
+        const int64_t ld = down ? v.lev_ld[lev + 1] : v.lev_ld[lev];
+        int dst = out;
+        const void *addend = nullptr;
+        int64_t ld_add = 0;
+        if (PL.add_dst[i] >= 0) {           // fused AddTable: the sum is stored, the convolution's own output never is
+          const int32_t *a = ops + OPW * (i + 1);
+          const int other = a[1] == out ? a[2] : a[1];
+          addend = B(other);
+          ld_add = LD(other);
+          dst = PL.add_dst[i];
+        }
+        void *wf = arena + L.aux_off[i];
+        PROG_TRY(sgnn_bf16_conv_prepare(P(par), cin, cout, K, 1, wf, stream));
+        PROG_TRY(sgnn_bf16_conv_run(B(in0), ROWS(in0), cin, LD(in0), P(par), wf, K, table, ld, n_out, cout, B(dst), LD(dst),
+                                    addend, ld_add, nullptr, 1, K, CNT(down ? lev + 1 : lev), stream));
+        break;
+      }
+      case OP_UNPOOL:
+        SGNN_CHECK_ARG(lev + 1 < nlev);
+        PROG_TRY(sgnn_bf16_gather_rows(B(in0), LD(in0), cin, (const int32_t *)v.lev_parent[lev], n, B(out), LD(out), CNT(lev),
+                                       stream));
+        break;
+      case OP_BN:
+        PROG_TRY(sgnn_bf16_bn_eval(B(in0), LD(in0), n, cin, P(par), P(par + 1), P(par + 2), P(par + 3), v.opf[4 * i],
+                                   v.opf[4 * i + 2], B(out), LD(out), CNT(lev), stream));
+        break;
+      case OP_ADD:
+        SGNN_CHECK_ARG(in1 >= 0);
+        PROG_TRY(sgnn_bf16_add(B(in0), LD(in0), B(in1), LD(in1), n, cin, B(out), LD(out), CNT(lev), stream));
+        break;
+      case OP_JOIN:
+        SGNN_CHECK_ARG(in1 >= 0);
+        PROG_TRY(sgnn_bf16_join(B(in0), LD(in0), cin, B(in1), LD(in1), cout, n, B(out), LD(out), CNT(lev), stream));
+        break;
+      case OP_CONCAT_IN: {
+        const int in2 = o[8];
+        SGNN_CHECK_ARG(in2 < nbuf && in0 < n_ext && in1 < n_ext && in2 < n_ext && CH(in0) + CH(in1) + CH(in2) == CH(out));
+        PROG_TRY(sgnn_bf16_concat3(EXT(in0), CH(in0), I(o[9]), EXT(in1), CH(in1), I(o[10]), EXT(in2), CH(in2), I(o[11]), n,
+                                   B(out), LD(out), CNT(lev), stream));
+        break;
+      }
+      case OP_EXPAND:
+        SGNN_CHECK_ARG(ROWS(out) == 8 * n);
+        PROG_TRY(sgnn_bf16_conv_expand_impl(B(in0), n, cin, LD(in0), P(par), (const int32_t *)v.lev_nbr[lev], v.lev_ld[lev],
+                                            cout, B(out), LD(out), CNT(lev), arena + L.aux_off[i], stream));
+        break;
+      case OP_LINEAR: {
+        SGNN_CHECK_ARG(cout >= 1 && cout <= 4 && PL.f32[out] && LD(out) == cout);
+        const float *w[4] = {}, *b[4] = {};
+        for (int q = 0; q < cout; ++q) {
+          w[q] = P(par + 2 * q);
+          b[q] = P(par + 2 * q + 1);
+        }
+        PROG_TRY(sgnn_bf16_linear_rows(B(in0), LD(in0), n, cin, w, b, cout, (float *)B(out), CNT(lev), stream));
+        break;
+      }
+      default:
+        sgnn_set_error("sgnn_prog_forward: unknown op %d", type);
+        return SGNN_EINVAL;
+    }
+  }
+  return SGNN_OK;
 }
 
 SGNN_EXPORT int sgnn_prog_forward(const int32_t *ops, const float *opf, int nops, const int32_t *bufs, int nbuf, int n_ext,
@@ -462,10 +632,15 @@ SGNN_EXPORT int sgnn_prog_forward(const int32_t *ops, const float *opf, int nops
                  n_ext >= 0 && n_ext <= nbuf && (n_ext == 0 || ext));
   View v{ops, opf, nops, bufs, nbuf, n_ext, lev_n, lev_ld, lev_nbr, lev_children, lev_ptable, lev_parent, nlev};
   Plan PL;
-  make_plan(v, keep, PL);
-  Layout L;
   const bool infer = (training & 2) != 0;     // inference layout: no backward call may follow
+  const bool bf16 = (training & 4) != 0;      // bf16 storage (inference layout only, eval only)
   training &= 1;
+  if (bf16 && (!infer || training)) {
+    sgnn_set_error("sgnn_prog_forward: bf16 storage needs the inference layout in eval mode (training = 2 | 4)");
+    return SGNN_EINVAL;
+  }
+  make_plan(v, keep, PL, bf16);
+  Layout L;
   SGNN_CHECK_ARG(make_layout(v, PL, L, infer, keep) == 0);
   if (arena_floats < L.fwd_total) {
     sgnn_set_error("sgnn_prog_forward: arena too small (%lld < %lld floats)", (long long)arena_floats,
@@ -476,6 +651,7 @@ SGNN_EXPORT int sgnn_prog_forward(const int32_t *ops, const float *opf, int nops
     sgnn_set_error("sgnn_prog_forward: workspace too small");
     return SGNN_ENOWS;
   }
+  if (bf16) return forward_bf16(v, PL, L, ext, idx, nidx, params, nparams, lev_cnt, arena, wait_event, stream);
   auto B = [&](int b) -> float * { return b < 0 ? nullptr : (b < n_ext ? (float *)ext[b] : arena + L.buf_off[b]); };
   auto LD = [&](int b) -> int64_t { return PL.ld[b]; };       // row stride (floats): wider than the channels for a view
   auto CH = [&](int b) { return b < 0 ? 0 : bufs[2 * b + 1]; };

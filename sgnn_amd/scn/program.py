@@ -13,6 +13,8 @@ node per layer (~110 per step) plus a dozen more per stage for the glue, and the
 
 The modules stay the parameter holders, so state-dict layout and results are unchanged (tests/test_gpu_program.py).
 """
+import contextlib
+
 import numpy as np
 import torch
 from torch.autograd import Function
@@ -38,7 +40,27 @@ _garenas = {}
 # not the shared per-device arena), the incoming output gradients, the level tables — is kept alive here.
 DEFER_JOIN = False
 _deferred = []
-_iarenas = {}      # inference: one forward arena per device, shared by all programs
+_iarenas = {}      # inference: one forward arena per device, shared by all programs (fp32 and bf16 layouts alike)
+_bf16_depth = 0    # > 0 inside bf16_inference()
+
+
+@contextlib.contextmanager
+def bf16_inference():
+    """Inside the context every program call in the inference layout (no gradient may be requested) stores its
+    intermediate feature rows as bf16 (sgnn_prog_forward training = 2 | 4: bf16 MFMA convolutions, fp32 math, one
+    rounding per stored value).  Program outputs stay fp32 tensors of the same shapes; everything outside the programs
+    is unchanged.  A call that would run in the training layout, or a BatchNorm in training mode, raises instead of
+    falling back to fp32.  Leaving the context restores the fp32 path exactly."""
+    global _bf16_depth
+    _bf16_depth += 1
+    try:
+        yield
+    finally:
+        _bf16_depth -= 1
+
+
+def bf16_active():
+    return _bf16_depth > 0
 
 
 ARENA_SHRINK_AFTER = 32     # calls in a row that used less than half of a persistent arena before it is re-allocated
@@ -144,6 +166,8 @@ class Program(object):
         self.bufs_np = np.ascontiguousarray(np.array(self.bufs, dtype=np.int32).reshape(-1, 2))
         self.subm_levels = sorted(set(o[5] for o in self.ops if o[0] in (OP_SUBM, OP_EXPAND)))
         self.n_idx = 1 + max([max(o[9:12]) for o in self.ops] + [-1])
+        self.linear_outs = set(o[3] for o in self.ops if o[0] == OP_LINEAR)    # fp32 in the bf16 layout too
+        self.has_bn = any(o[0] == OP_BN for o in self.ops)
 
     def _class(self, name):
         if name not in self._classes:
@@ -338,9 +362,10 @@ class _ProgramFn(Function):
         run.keep = keep
         qa = (ops.ctypes.data, nops, bufs.ctypes.data, nbuf, n_ext, lev_n.ctypes.data, ncls, keep.ctypes.data)
         infer = bool(run.infer)
+        bf16 = bool(run.bf16)
         # gradient arena (backward: buffers + scratch) / forward arena (buffers only; liveness-packed for inference)
         total = _lib.query('sgnn_prog_arena_floats', *qa, 0)
-        fwd_total = _lib.query('sgnn_prog_arena_floats', *qa, 2 if infer else 1)
+        fwd_total = _lib.query('sgnn_prog_arena_floats', *qa, 3 if bf16 else (2 if infer else 1))
         wsb = _lib.query('sgnn_prog_ws_bytes', ops.ctypes.data, nops, lev_n.ctypes.data, ncls)
         run.total, run.wsb = total, wsb
         prog.last_arena_floats = (fwd_total, total)
@@ -360,15 +385,21 @@ class _ProgramFn(Function):
                   run.tabs[2].ctypes.data, run.tabs[3].ctypes.data, run.tabs[4].ctypes.data, ncls,
                   run.pptr.ctypes.data, len(params),
                   run.eptr.ctypes.data, run.iptr.ctypes.data, len(run.idx), arena.data_ptr(), fwd_total,
-                  keep.ctypes.data, int(run.training) | (2 if infer else 0), wait, ws.data_ptr(), wsb)
+                  keep.ctypes.data, int(run.training) | (2 if infer else 0) | (4 if bf16 else 0), wait, ws.data_ptr(), wsb)
         _lib.stamp('prog>')
         run.offsets = {}
         outs = []
         for b in run.out_bufs:
-            off = _lib.query('sgnn_prog_buffer_offset', *qa, int(infer), b)
+            off = _lib.query('sgnn_prog_buffer_offset', *qa, 2 if bf16 else int(infer), b)
             assert off >= 0
             rows, ch = int(lev_n[bufs[b, 0]]), int(bufs[b, 1])
             run.offsets[b] = (off, rows, ch)
+            if bf16 and b not in prog.linear_outs:
+                # bf16 rows, stride = channels rounded up to 8 (sgnn_prog_arena_floats mode 3) -> contiguous fp32
+                o = torch.empty(rows, ch, dtype=torch.float32, device=dev)
+                _lib.call('sgnn_bf16_to_f32', arena.data_ptr() + 4 * off, (ch + 7) // 8 * 8, rows, ch, o.data_ptr(), None)
+                outs.append(o)
+                continue
             o = arena[off:off + rows * ch].view(rows, ch)
             # inference: the arena is dropped (or handed to the next program) right away, only the outputs stay
             outs.append(o.clone() if infer else o)
@@ -477,6 +508,14 @@ def run_program(prog, x, training, out_bufs=None, ext=None, idx=(), extra_rows=N
     # nothing will ask for a gradient: inference layout (buffers share storage by liveness, outputs copied out)
     run.infer = not (torch.is_grad_enabled() and any(t is not None and t.requires_grad
                                                      for t in list(tensors) + list(prog.tensors())))
+    run.bf16 = bf16_active()
+    if run.bf16 and not run.infer:
+        raise RuntimeError('bf16_inference: this program call may be asked for gradients (grad mode is on and an input '
+                           'or parameter requires grad); bf16 storage exists for inference only — wrap the forward in '
+                           'torch.no_grad() or leave the bf16_inference() context')
+    if run.bf16 and training and prog.has_bn:
+        raise RuntimeError('bf16_inference: BatchNorm in training mode (batch statistics) is not available with bf16 '
+                           'storage; call model.eval() first')
     if 'child' in prog.class_ids and 'child' not in run.extra_rows:
         run.extra_rows['child'] = 8 * run.grids[0].n
     outs = _ProgramFn.apply(run, *tensors, *prog.tensors())

@@ -131,12 +131,12 @@ __device__ __forceinline__ void conv_fwd_body(const float *__restrict__ x, int64
     }
   };
   auto mma_b = [&](float(&a)[M][V], const float(&b)[NT][V]) {
-    if constexpr (CINP != CIN) {  // the last quarter reads past the row end: those slots must be exact zeros
+    if constexpr (CINP != CIN) {  // the quarters past the row end read other channels: those slots must be exact zeros
 #pragma unroll
       for (int m = 0; m < M; ++m)
 #pragma unroll
         for (int s = 0; s < V; ++s)
-          if (3 * V + s >= CIN) a[m][s] = (q == 3) ? 0.f : a[m][s];
+          if (3 * V + s >= CIN) a[m][s] = (q >= conv_first_pad_quarter<CIN, V>(s)) ? 0.f : a[m][s];
     }
 #pragma unroll
     for (int s = 0; s < V; ++s)
@@ -338,10 +338,10 @@ __global__ __launch_bounds__(256) void k_conv_small(const float *__restrict__ x,
         const int n = nt * 16 + r;
         const bool okw = kk < nk && n < COUT;
         buf_load_floats<V>(rs_w, okw ? (uint32_t)((ks * COUT + n) * CIN + q * V) * 4u : 0xFFFFF800u, b[kk][nt]);
-        if constexpr (CINP != CIN) {   // the last quarter runs into the next column's weights: those slots are zero
+        if constexpr (CINP != CIN) {   // the quarters past CIN run into the next column's weights: those slots are zero
 #pragma unroll
           for (int s = 0; s < V; ++s)
-            if (3 * V + s >= CIN) b[kk][nt][s] = (q == 3) ? 0.f : b[kk][nt][s];
+            if (3 * V + s >= CIN) b[kk][nt][s] = (q >= conv_first_pad_quarter<CIN, V>(s)) ? 0.f : b[kk][nt][s];
         }
       }
     }
@@ -419,7 +419,7 @@ __global__ __launch_bounds__(256) void k_conv_small(const float *__restrict__ x,
     for (int kk = 0; kk < KW; ++kk)
 #pragma unroll
       for (int s = 0; s < V; ++s)
-        if (3 * V + s >= CIN) a[kk][s] = (q == 3) ? 0.f : a[kk][s];
+        if (3 * V + s >= CIN) a[kk][s] = (q >= conv_first_pad_quarter<CIN, V>(s)) ? 0.f : a[kk][s];
   }
   f32x4 acc[2][NT];
 #pragma unroll

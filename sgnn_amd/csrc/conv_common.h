@@ -25,6 +25,12 @@ struct ConvCfg {
   static constexpr int ALIGN = ((CIN % 4 == 0) && (V % 4 == 0)) ? 16 : (((CIN % 2 == 0) && (V % 2 == 0)) ? 8 : 4);
 };
 
+// slot s of lane quarter q holds input channel q*V + s: a pad channel (>= CIN, must be an exact zero) iff q >= this.  Only
+// the last quarter is partial when CINP - CIN < V (then this is 3 for the slots 3V + s >= CIN); at CIN = 1 or 2 (V = 1)
+// quarters 1 and 2 hold pad channels too.
+template <int CIN, int V>
+__device__ __forceinline__ constexpr int conv_first_pad_quarter(int s) { return (CIN - s + V - 1) / V; }
+
 // optional generalisation of the rulebook walk (sgnn_conv_*_ex): offset k of group g reads table row
 // kmap[g*K + k] (NULL: k), gathers feature row idx*in_mul + kadd[g*K + k] (NULL: +0) and group g owns output rows
 // row*groups + g and the weight block g.  Plain convolutions use {NULL, NULL, 1, 1}.

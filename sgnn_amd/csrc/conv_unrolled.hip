@@ -94,8 +94,8 @@ __device__ __forceinline__ void conv_fwd_u_body(const float *__restrict__ x, int
 #pragma unroll
       for (int m = 0; m < M; ++m) {
         float av = a[k & 1][m][s];
-        if constexpr (CINP != CIN)       // the last quarter reads past the row end: those slots must be exact zeros
-          if (3 * V + s >= CIN) av = (q == 3) ? 0.f : av;
+        if constexpr (CINP != CIN)       // the quarters past the row end read other channels: those slots must be exact zeros
+          if (3 * V + s >= CIN) av = (q >= conv_first_pad_quarter<CIN, V>(s)) ? 0.f : av;
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
           acc[m][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b[nt][s], acc[m][nt], 0, 0, 0);

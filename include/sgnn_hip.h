@@ -694,6 +694,45 @@ int sgnn_io_scatter_dense(const uint32_t *locs_xyz, const float *vals, const flo
                           float *dense, sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * TSDF fusion: depth frames -> scan volume -> .sdf / .knw blocks or the collated scene input (the step of
+ * datagen/GenerateScans that produces the files above; rules in INTEGRATION.md "TSDF fusion").
+ * Volumes are dense (dz, dy, dx) arrays, x fastest: sdf f32 in metres (-inf = never observed), weight u8,
+ * free counter i32.  Depth frames are one (nframes, h, w) f32 stack in metres, -inf = invalid.
+ * ------------------------------------------------------------------------- */
+/* one frame of sgnn_fuse_integrate (96 bytes; the frame table is a device array of these) */
+typedef struct sgnn_fuse_frame {
+  float m[12];    /* rows 0..2 of inv(cam2world) * inv(world2grid): voxel (i,j,k,1) -> camera, fp32 */
+  float intr[4];  /* fx, fy, cx, cy */
+  int32_t box[6]; /* frustum box in voxels, inclusive: x0, x1, y0, y1, z0, z1 (empty when x0 > x1 or ...) */
+  int64_t offset; /* element offset of this frame's (h, w) image in the depth stack */
+} sgnn_fuse_frame;
+/* out[f][j][i] = metric depth of raw[f] (nframes, h_raw, w_raw) u16 resampled to (h, w) by nearest index
+ * round(i * (w_raw-1)/(w-1)): (1/depth_shift) * d, -inf where d == 0 or outside [min_depth, max_depth] */
+int sgnn_fuse_depth_raw(const uint16_t *raw, int nframes, int h_raw, int w_raw, int h, int w, float depth_shift,
+                        float min_depth, float max_depth, float *out, sgnn_stream_t stream);
+/* bilateral filter of every frame (radius ceil(2 sigma_d)); in and out must not alias */
+int sgnn_fuse_bilateral(const float *in, int nframes, int h, int w, float sigma_d, float sigma_r, float *out,
+                        sgnn_stream_t stream);
+/* integrate frames 0..nframes-1 in order into (sdf, weight, free_ctr), `chunk` frames per launch (<= 0: all; the
+ * result does not depend on it).  obb: host float[12] = corner a, edges e0, e1, e2 in voxel coordinates, or NULL */
+int sgnn_fuse_integrate(float *sdf, uint8_t *weight, int32_t *free_ctr, int dx, int dy, int dz, const float *depth,
+                        int h, int w, const sgnn_fuse_frame *frames, int nframes, int chunk, float voxel_size,
+                        float depth_min, float depth_max, const float *obb, sgnn_stream_t stream);
+/* mask[v] = |sdf[v]| <= keep_abs, and — truncation > 0 — |sdf[v] / voxel_size| < truncation and z < max_z */
+int sgnn_fuse_flag(const float *sdf, int dx, int dy, int dz, float keep_abs, float truncation, float voxel_size,
+                   int64_t max_z, uint8_t *mask, sgnn_stream_t stream);
+/* rows q < *count (sel from sgnn_compact_mask of the flags): locs_xyz[q] = (x, y, z) u32 and vals[q] = sdf, the
+ * layout of an .sdf block */
+int sgnn_fuse_emit_block(const float *sdf, int dx, int dy, const int32_t *sel, const int64_t *count, int64_t n_max,
+                         uint32_t *locs_xyz, float *vals, sgnn_stream_t stream);
+/* the same as collated scene input: locs[q] = {z, y, x, 0} int64, feats[q] = sdf / voxel_size */
+int sgnn_fuse_emit_rows(const float *sdf, int dx, int dy, float voxel_size, const int32_t *sel, const int64_t *count,
+                        int64_t n_max, int64_t *locs, float *feats, sgnn_stream_t stream);
+/* u8 known codes of the .knw file: sdf < -vs -> max(2, min(255, (int)(-sdf/vs) + 1)), sdf <= vs -> 1, else 0;
+ * -inf -> 2 */
+int sgnn_fuse_known(const float *sdf, int64_t n, float voxel_size, uint8_t *known, sgnn_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Evaluation metrics on the device.
  * ------------------------------------------------------------------------- */
 /* IoU ingredients of one hierarchy level (torch/loss.py:84-120 compute_iou_sparse_dense, fed as in

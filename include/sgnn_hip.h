@@ -151,6 +151,10 @@ typedef struct sgnn_tune {
    * torch/model.py:230-243): 1 = the head's kernel writes dy w + that gradient in one pass; 0 = an add launch over the level
    * follows.  Same sums (one fp32 addition per element either way).  Default 1. */
   int64_t prog_lin_add;
+  /* BatchNorm forward / backward (bn.hip): 1 = small levels (c <= 64, few statistics partials) finalise the statistics
+   * inside the apply kernels, as bn_fuse_ok decides; 0 = always the separate finalize kernels.  The two add the fp64
+   * partials in different fixed orders (fp64 round-off before the fp32 results).  Default 1. */
+  int64_t bn_fuse;
 } sgnn_tune;
 int64_t sgnn_tune_set(const char *name, int64_t value);
 int64_t sgnn_tune_get(const char *name);

@@ -2,9 +2,12 @@
 // 181,187,256 and the FullyConvolutionalNet bodies).
 //
 // HBM-bound row passes over a row-major (N, C) slab:
-//   stats  : one read  — per-thread fp32 partial sums over a short run of rows, flushed into
-//            fp64 accumulators (keeps E[x^2]-E[x]^2 exact to fp32 resolution), workgroup
-//            tree in LDS, per-workgroup partials reduced in fixed order (deterministic);
+//   stats  : one read  — per-thread fp32 partial sums over BN_FLUSH rows, flushed into fp64
+//            accumulators, workgroup tree in LDS, per-workgroup partials reduced in fixed order
+//            (deterministic).  Each x and x^2 is rounded to fp32 at most twice before it reaches
+//            fp64, so E[x^2]-E[x]^2 is within ~2^-22 (var + mean^2) of the exact variance: relative
+//            to var + mean^2, not to var (data whose mean is large next to its spread loses the
+//            low bits of var; tests/bn_ref.py holds the kernels to 2^-20 (var + mean^2));
 //   apply  : one read + one write, float4 when C % 4 == 0;
 //   bwd    : reduce pass (dy, x read) + apply pass (dy, x read, dx written).
 // Thread mapping keeps a thread on a fixed channel group: blockDim = RPB rows x CQ column
@@ -571,6 +574,10 @@ int sgnn_bn_fwd_impl(const float *x, int64_t ldx, int64_t n, int c, const float 
   SGNN_CHECK_ARG(ldx >= c && ldy >= c);
   BnGeom g = bn_geom(c);
   if (g.vec == 4 && (ldx % 4 || ldy % 4 || ((uintptr_t)x & 15) || ((uintptr_t)y & 15))) g = bn_geom_scalar(c);
+  if (g.cq > 256) {   // one thread per column group: the scalar kernels cover 256 channels
+    sgnn_set_error("sgnn_bn_fwd: %d channels need 16-byte aligned rows (row strides multiples of 4 floats)", c);
+    return SGNN_EINVAL;
+  }
   BnFuse fuse{nullptr, 0, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   if (training && n > 0) {
     SGNN_CHECK_ARG(x);
@@ -591,7 +598,7 @@ int sgnn_bn_fwd_impl(const float *x, int64_t ldx, int64_t n, int c, const float 
                            g.cq, g.rpb, nullptr, nullptr, nullptr, nullptr, 0.f, (double *)ws, n_dev, BnLin{});
       partial = (const double *)ws;
     }
-    if (bn_fuse_ok(nblk, c, bn_apply_grid(n, g)))   // small level: k_bn_apply finalises
+    if (g_tune.bn_fuse && bn_fuse_ok(nblk, c, bn_apply_grid(n, g)))   // small level: k_bn_apply finalises
       fuse = BnFuse{partial, (int)nblk, eps, momentum, running_mean, running_var, save_mean, save_invstd, nullptr, nullptr};
     else
       SGNN_LAUNCH(k_bn_finalize_fwd, dim3(c), dim3(256), 0, s, partial, (int)nblk, n, c, eps, momentum,
@@ -690,6 +697,10 @@ int sgnn_bn_bwd_impl(const float *x, int64_t ldx, const float *dy, int64_t ld_dy
   if (g.vec == 4 && (ldx % 4 || ld_dy % 4 || ld_dx % 4 || ld_add % 4 || ((uintptr_t)x & 15) || ((uintptr_t)dy & 15) ||
                      ((uintptr_t)dx & 15) || ((uintptr_t)addend & 15)))
     g = bn_geom_scalar(c);
+  if (g.cq > 256) {   // one thread per column group: the scalar kernels cover 256 channels
+    sgnn_set_error("sgnn_bn_bwd: %d channels need 16-byte aligned rows (row strides multiples of 4 floats)", c);
+    return SGNN_EINVAL;
+  }
   const double *partial = pre_partial;
   int64_t nblk = pre_nblk;
   // the coefficient block always lives behind the largest partial table this library writes into ws
@@ -712,7 +723,7 @@ int sgnn_bn_bwd_impl(const float *x, int64_t ldx, const float *dy, int64_t ld_dy
     partial = (const double *)ws;
   }
   BnFuse fuse{nullptr, 0, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (bn_fuse_ok(nblk, c, bn_apply_grid(n, g)))
+  if (g_tune.bn_fuse && bn_fuse_ok(nblk, c, bn_apply_grid(n, g)))
     fuse = BnFuse{partial, (int)nblk, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, dgamma, dbeta};
   else
     SGNN_LAUNCH(k_bn_finalize_bwd, dim3(c), dim3(256), 0, s, partial, (int)nblk, n, c, dgamma, dbeta, coef, n_dev);

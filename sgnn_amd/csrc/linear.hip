@@ -161,9 +161,21 @@ SGNN_EXPORT int64_t sgnn_linear_ws_bytes(int64_t n, int cin, int cout) {
 
 #define LIN_CASES(X) X(16, 1) X(16, 2) X(48, 1) X(48, 2) X(8, 1) X(8, 2) X(32, 1) X(32, 2) X(12, 2) X(4, 1)
 
+// an uncompiled head shape is an error at every row count, an empty level included (before anything is written)
+static bool lin_shape_ok(int cin, int cout) {
+#define X(CI, CO) if (cin == CI && cout == CO) return true;
+  LIN_CASES(X)
+#undef X
+  return false;
+}
+
 int sgnn_linear_fwd_rows(const float *x, int64_t n, int cin, const float *const *w, const float *const *b, int cout,
                          float *y, sgnn_stream_t stream, const int64_t *n_dev) {
   SGNN_CHECK_ARG(n >= 0 && cin >= 1 && cout >= 1 && cout <= LIN_MAX_OUT);
+  if (!lin_shape_ok(cin, cout)) {
+    sgnn_set_error("sgnn_linear_fwd: unsupported head shape %d -> %d", cin, cout);
+    return SGNN_EINVAL;
+  }
   if (n == 0) return SGNN_OK;
   SGNN_CHECK_ARG(x && w && y);
   LinW p{};
@@ -207,6 +219,10 @@ int sgnn_linear_bwd_rows(const float *x, const float *dy, int64_t n, int cin, co
   hipStream_t s = (hipStream_t)stream;
   SGNN_CHECK_ARG(n >= 0 && cin >= 1 && cout >= 1 && cout <= LIN_MAX_OUT && w);
   SGNN_CHECK_ARG(!addend || (dx && ld_add >= cin && (cin % 4 != 0 || (ld_add % 4 == 0 && ((uintptr_t)addend & 15) == 0))));
+  if (!lin_shape_ok(cin, cout)) {
+    sgnn_set_error("sgnn_linear_bwd: unsupported head shape %d -> %d", cin, cout);
+    return SGNN_EINVAL;
+  }
   if (n == 0) {
     for (int o = 0; o < cout; ++o) {
       if (dw && dw[o]) SGNN_HIP_TRY(hipMemsetAsync(dw[o], 0, (size_t)cin * sizeof(float), s));

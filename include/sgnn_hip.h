@@ -91,7 +91,7 @@ int sgnn_hash_lookup(const uint64_t *keys, const int32_t *vals, int64_t cap, con
  * says what stays bit-identical).  No reference counterpart.  Set by name: sgnn_tune_set("conv_wide_epi", 0) returns the
  * previous value, SGNN_TUNE_UNKNOWN (with sgnn_last_error) for an unknown name or a value out of range; sgnn_tune_get reads;
  * sgnn_tune_names = the comma-separated field names; sgnn_tune_current = the live table (read-only).  Process-global, not
- * thread-safe: set them before the work they steer (workspace sizes follow conv_bwd_fused / conv_bwd_fused_rows).
+ * thread-safe: set them before the work they steer (workspace sizes follow conv_small_rows / conv_dw_blocks).
  * Host layer: sgnn_amd._lib.tune(name, value); environment SGNN_TUNE="name=value,name=value" at load.
  * ------------------------------------------------------------------------- */
 #define SGNN_TUNE_UNKNOWN INT64_MIN
@@ -122,15 +122,6 @@ typedef struct sgnn_tune {
   /* weight gradient of a one-channel input (1 -> 8, the network's first convolution): 1 = the register-accumulating VALU
    * kernel, 0 = the MFMA kernel of the other shapes.  Different summation order (fp32 round-off).  Default 1. */
   int64_t conv_dw_c1;
-  /* 1 = sgnn_prog_backward runs 16-channel 3x3x3 layers on levels of >= conv_bwd_fused_rows rows through the fused backward
-   * kernel (sgnn_conv_bwd_fused: dX and dW from one gather of dy).  dX rows bit-identical, dW another fixed summation
-   * order.  Default 0: 0.95x the two kernels stand-alone, +0.04 .. +0.14 ms per step (profiles/r06_fused_backward.txt). */
-  int64_t conv_bwd_fused;
-  int64_t conv_bwd_fused_rows;   /* >= 256.  Default 40 960. */
-  /* 1 = the 3x3x3 rulebook builder hashes the voxel index of a 768-row window around each 256-row tile into LDS (global
-   * table only for neighbours not found there); 0 = the global-probe kernel, faster on MI355X (96.7 vs 123.9 us at N =
-   * 366 k).  Identical tables.  Default 0. */
-  int64_t rulebook_lds;
   /* sgnn_rulebook_subm3_multi: 1 = all levels in one pre-fill launch and one builder launch, 0 = one sgnn_rulebook_subm3
    * per level.  Identical tables.  Default 1. */
   int64_t rulebook_multi;
@@ -312,26 +303,6 @@ int64_t sgnn_conv_bwd_weight_ws_bytes(int64_t n_out, int K, int cin, int cout);
 int sgnn_conv_bwd_weight(const float *x, int64_t n_in, int cin, const float *dy, int cout,
                          const int32_t *table, int64_t ld, int K, int64_t n_out, float *dw, int in_shift, void *ws,
                          int64_t ws_bytes, sgnn_stream_t stream);
-
-/* Backward of a 3x3x3 SubmanifoldConvolution as ONE launch (round 6): data gradient and weight gradient from a single
- * gather of dy (torch/model.py:38,40,180,255 under train.py:262).  dy: (n, cout) rows with stride ld_dy; x: the layer's input
- * rows (n, cin), stride ldx; w: (27, cin, cout); table / ld: the level's neighbour table (sgnn_rulebook_subm3*);
- * dx: (n, cin) rows with stride ld_dx = sum_k dy[table[k][i]] W[26 - k]^T, with the epilogue options of sgnn_conv_fwd_epi
- * (addend, which may alias dx; stats = 2: BatchNorm-backward statistics partials, sgnn_conv_stats_blocks(n) x 2 x cin doubles);
- * dw: (27, cin, cout) = what sgnn_conv_bwd_weight returns (another fixed summation order), through per-workgroup partials in
- * ws (sgnn_conv_bwd_fused_ws_bytes) and the library's fixed-order reduce.  dx rows are bit-identical to
- * sgnn_conv_fwd_epi(flags = TRANSPOSE_W | FLIP_K).  Served shapes: sgnn_conv_bwd_fused_supported (cin = cout = 16, K = 27,
- * levels of at least sgnn_tune.conv_bwd_fused_rows rows, default 40 960); others return SGNN_EINVAL.  Row strides multiples of
- * 4 floats, bases 16-byte aligned.  n_dev: capacity mode (NULL = n is exact).  sgnn_tune.conv_bwd_fused = 1 makes
- * sgnn_prog_backward use it (default 0: stand-alone it is 0.95x the two kernels it replaces, in the step it costs
- * +0.04 .. +0.14 ms — profiles/r06_fused_backward.txt); set it before the first step (workspace sizes follow it). */
-int64_t sgnn_conv_bwd_fused_ws_bytes(int64_t n, int cin, int cout);
-int sgnn_conv_bwd_fused_supported(int64_t n, int cin, int cout, int K);
-int sgnn_conv_bwd_fused(const float *dy, int64_t n, int cout, int64_t ld_dy, const float *x, int cin, int64_t ldx,
-                        const float *w, const int32_t *table, int64_t ld, float *dx, int64_t ld_dx, const float *addend,
-                        int64_t ld_add, int stats, double *partial, const float *bn_x, int64_t ld_bnx, const float *mean,
-                        const float *invstd, const float *gamma, const float *beta, float leak, float *dw, void *ws,
-                        int64_t ws_bytes, const int64_t *n_dev, sgnn_stream_t stream);
 
 /* pre-summed weights of the generative up-sampling convolution and their gradient: Wc (64, cin, cout) from the layer's
  * W (27, cin, cout); dW from dWc (see sgnn_conv_fwd_ex) */

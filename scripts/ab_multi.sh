@@ -1,7 +1,7 @@
 #!/bin/bash
 # same-box comparison of several environment settings on the working tree, two interleaved rounds; each argument is a
 # space-separated list of VAR=value pairs ("-" = the defaults):
-#   scripts/ab_multi.sh - "SGNN_TUNE=sgnn_prog_set_bn_fold=1,sgnn_prog_set_bn_fold_rows=40000" "SGNN_DENSE_RULEBOOK_MIN_ROWS=4096"
+#   scripts/ab_multi.sh - "SGNN_TUNE=conv_dw_blocks=341,prog_lin_bn=0" "SGNN_DENSE_RULEBOOK_MIN_ROWS=4096"
 # prints: setting, blocks/s, ms/step, library launches per step, convolution ms per step (HIP events, eager roofline leg)
 for round in 1 2; do
   for v in "$@"; do

@@ -53,7 +53,7 @@ __global__ __launch_bounds__(256) void k_mfma_data(float *out, const float *in, 
   if (s == 12345.678f) out[blockIdx.x * 256 + threadIdx.x] = s;
 }
 
-// mode "stage" (round 6): the MFMA stream of one offset of the fused backward kernel (csrc/conv_bwd_fused.hip): 4 dX MFMAs on
+// mode "stage" (round 6): the MFMA stream of one offset of the fused backward kernel (profiles/r06_fused_backward.txt): 4 dX MFMAs on
 // four accumulators, then 12 x (dW on one accumulator, dX), then 4 dW; operands from 32 + 8 different registers; two waves per
 // SIMD.  NK = 27: the 27 offsets unrolled with 27 dW accumulators (the kernel's shape, ~25 KB of code); NK = 1: one stage in a
 // loop (same instruction mix, a few hundred bytes of code).

@@ -43,7 +43,7 @@ struct ConvEx {
 };
 
 // resident workgroups of a 256-thread kernel on the whole device (occupancy x CUs), cached per instantiation: the large-level
-// kernels size their row tiles so that ONE round of workgroups covers the level (k_conv_fwd; sgnn_conv_set_one_round)
+// kernels size their row tiles so that ONE round of workgroups covers the level (k_conv_fwd; sgnn_tune.conv_one_round)
 // Per DEVICE (a process may drive several) and thread-safe: relaxed atomics, every thread that races computes the same value.
 // A failed query is NOT cached (0 = "one-round mode off" would otherwise stick for the life of the process).  The J-tile
 // decomposition of a level — and with it the fp64 grouping of the BatchNorm statistics partials — follows this value, so

@@ -284,113 +284,6 @@ __global__ __launch_bounds__(256) void k_rulebook_subm3_multi(RbMulti b) {
 //  its pre-fill (27 x {key, slot, probe} live per thread; 44 vs 16 us at 12.6 k rows, 27 vs 14 us at 2.7 k rows under
 //  rocprofv3, profiles/r05w_step_launches.csv) for a launch that costs < 2 us in a replayed graph: deleted.)
 // ---------------------------------------------------------------------------
-// The same rulebook with the voxel index of a row WINDOW held in LDS (north_star: "hash-table voxel indexing in LDS").
-// A workgroup owns 256 consecutive rows; in every site order this pipeline produces — batch-major raster order of the
-// input blocks (scene_dataloader.py:13-36), 8-children-per-parent order of the generated levels (model.py:195-207) —
-// most of a row's 26 neighbours are rows close by.  The workgroup hashes the coordinates of the rows [row0 - 256,
-// row0 + 512) into a 2048-slot LDS table, every site probes its 26 neighbours THERE (a hit is final), and only the
-// misses — neighbours that do not exist, or live outside the window — go to the global table.  All 27 table rows are
-// written by the site's own thread (coalesced): no mirror scatter, no pre-fill memset.
-// ---------------------------------------------------------------------------
-#define RB_WIN_BEFORE 256
-#define RB_WIN_ROWS 768
-#define RB_LDS_SLOTS 2048
-
-__global__ __launch_bounds__(256) void k_rulebook_subm3_lds(const uint64_t *__restrict__ keys,
-                                                           const int32_t *__restrict__ vals, uint64_t mask,
-                                                           const int4 *__restrict__ coords, int64_t n,
-                                                           int32_t *__restrict__ nbr, int64_t ld,
-                                                           const int64_t *n_dev) {
-  n = sgnn_dyn_n(n, n_dev);
-  __shared__ unsigned long long lk[RB_LDS_SLOTS];
-  __shared__ int32_t lv[RB_LDS_SLOTS];
-  const int tid = threadIdx.x;
-  const int64_t row0 = (int64_t)blockIdx.x * 256;
-  const int64_t wlo = row0 > RB_WIN_BEFORE ? row0 - RB_WIN_BEFORE : 0;
-  const int64_t whi = (wlo + RB_WIN_ROWS) < n ? (wlo + RB_WIN_ROWS) : n;
-  for (int e = tid; e < RB_LDS_SLOTS; e += 256) lk[e] = SGNN_EMPTY_KEY;
-  __syncthreads();
-  for (int64_t i = wlo + tid; i < whi; i += 256) {
-    const int4 c = coords[i];
-    const unsigned long long key = sgnn_pack_key(c.x, c.y, c.z, c.w);
-    unsigned slot = (unsigned)sgnn_hash64(key) & (RB_LDS_SLOTS - 1);
-    while (true) {
-      const unsigned long long prev = atomicCAS(&lk[slot], SGNN_EMPTY_KEY, key);
-      if (prev == SGNN_EMPTY_KEY) {
-        lv[slot] = (int32_t)i;
-        break;
-      }
-      if (prev == key) break;                 // duplicate site: the caller error is reported by sgnn_hash_build
-      slot = (slot + 1) & (RB_LDS_SLOTS - 1);
-    }
-  }
-  __syncthreads();
-  const int64_t j = row0 + tid;
-  if (j >= ld) return;
-  if (j >= n) {
-#pragma unroll
-    for (int k = 0; k < 27; ++k) nbr[(int64_t)k * ld + j] = -1;
-    return;
-  }
-  const int4 c = coords[j];
-  int32_t r[27];
-  unsigned missing = 0;                       // bit k: neighbour k was not in the LDS window
-#pragma unroll
-  for (int k = 0; k < 27; ++k) {
-    if (k == 13) {
-      r[k] = (int32_t)j;
-      continue;
-    }
-    const int dz = k / 9 - 1, dy = (k / 3) % 3 - 1, dx = k % 3 - 1;
-    const int z = c.x + dz, y = c.y + dy, x = c.z + dx;
-    r[k] = -1;
-    if (((unsigned)z > 65535u) || ((unsigned)y > 65535u) || ((unsigned)x > 65535u)) continue;
-    const unsigned long long key = sgnn_pack_key(z, y, x, c.w);
-    unsigned slot = (unsigned)sgnn_hash64(key) & (RB_LDS_SLOTS - 1);
-    bool hit = false;
-    while (true) {
-      const unsigned long long kk = lk[slot];
-      if (kk == key) {
-        hit = true;
-        break;
-      }
-      if (kk == SGNN_EMPTY_KEY) break;
-      slot = (slot + 1) & (RB_LDS_SLOTS - 1);
-    }
-    if (hit) r[k] = lv[slot];
-    else missing |= 1u << k;
-  }
-  // the misses: first-slot key loads of all of them in flight together, then the (rare) longer probe walks
-  uint64_t gk[27];
-  uint64_t gs[27];
-#pragma unroll
-  for (int k = 0; k < 27; ++k) {
-    if (!((missing >> k) & 1u)) continue;
-    const int dz = k / 9 - 1, dy = (k / 3) % 3 - 1, dx = k % 3 - 1;
-    const uint64_t key = sgnn_pack_key(c.x + dz, c.y + dy, c.z + dx, c.w);
-    gs[k] = sgnn_hash64(key) & mask;
-    gk[k] = keys[gs[k]];
-  }
-#pragma unroll
-  for (int k = 0; k < 27; ++k) {
-    if (!((missing >> k) & 1u)) continue;
-    const int dz = k / 9 - 1, dy = (k / 3) % 3 - 1, dx = k % 3 - 1;
-    const uint64_t key = sgnn_pack_key(c.x + dz, c.y + dy, c.z + dx, c.w);
-    uint64_t sl = gs[k], kk = gk[k];
-    while (kk != key && kk != SGNN_EMPTY_KEY) {
-      sl = (sl + 1) & mask;
-      kk = keys[sl];
-    }
-    if (kk == key) r[k] = vals[sl];
-  }
-#pragma unroll
-  for (int k = 0; k < 27; ++k) nbr[(int64_t)k * ld + j] = r[k];
-}
-
-// Measured (scripts/bench_conv.py, MI355X): N = 366 085 raster-ordered sites 123.9 us vs 96.7 us for the global-probe kernel
-// (incl. its memset), N = 2 017 264 children-ordered sites 661 vs 498 us: the 26 dependent LDS probe walks + 768 LDS CAS
-// inserts per workgroup cost more than the 13 L2-resident global probes they replace, so the global kernel is the default.
-// ---------------------------------------------------------------------------
 // The same rulebook through a dense index volume: vol[((b*Z + z)*Y + y)*X + x] = row of the site, -1 elsewhere.  A
 // neighbour look-up is then ONE 4-byte read next to the reads of the neighbouring threads (sites arrive in raster or
 // children order) instead of a hash probe into a random 8-byte key plus the value read, and all 27 entries of a site
@@ -531,12 +424,6 @@ SGNN_EXPORT int sgnn_rulebook_subm3(const uint64_t *keys, const int32_t *vals, i
   SGNN_CHECK_ARG(n >= 0 && ld >= n && keys && vals && cap >= 2 && (cap & (cap - 1)) == 0);
   if (n == 0) return SGNN_OK;
   SGNN_CHECK_ARG(coords && nbr);
-  if (g_tune.rulebook_lds) {
-    SGNN_LAUNCH(k_rulebook_subm3_lds, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, (hipStream_t)stream, keys,
-                       vals, (uint64_t)(cap - 1), (const int4 *)coords, n, nbr, ld, n_dev);
-    SGNN_CHECK_LAUNCH();
-    return SGNN_OK;
-  }
   if (n_dev)      // capacity mode: pre-fill only what the live rows can reach
     SGNN_LAUNCH(k_fill_rows_dyn, dim3(sgnn_grid_for(13 * n, 256, 4096)), dim3(256), 0, (hipStream_t)stream,
                        nbr + 14 * ld, 13, ld, n, n_dev);
@@ -555,7 +442,7 @@ SGNN_EXPORT int sgnn_rulebook_subm3_multi(int count, const uint64_t *const *keys
   SGNN_CHECK_ARG(count >= 0 && count <= SGNN_RULEBOOK_MULTI_MAX);
   if (count == 0) return SGNN_OK;
   SGNN_CHECK_ARG(keys && vals && caps && coords && ns && nbrs && lds && n_devs);
-  if (!g_tune.rulebook_multi || g_tune.rulebook_lds) {
+  if (!g_tune.rulebook_multi) {
     for (int i = 0; i < count; ++i) {
       SGNN_CHECK_ARG(ns[i] == 0 || n_devs[i]);
       const int rc = sgnn_rulebook_subm3(keys[i], vals[i], caps[i], coords[i], ns[i], nbrs[i], lds[i], n_devs[i], stream);

@@ -377,14 +377,7 @@ inline int64_t expand_dwc_bytes(int cin, int cout) { return (64 * (int64_t)cin *
 int64_t dw_slice(const View &v, int i) {   // workspace slice of op i's weight-gradient partials (256-byte multiple)
   const int32_t *o = v.ops + OPW * i;
   int64_t w = 0;
-  if (o[0] == OP_CONV_SUBM) {
-    w = sgnn_conv_bwd_weight_ws_bytes(v.lev_n[o[5]], 27, o[6], o[7]);
-    // the fused backward kernel keeps one partial per resident workgroup (conv_bwd_fused.hip)
-    if (sgnn_conv_bwd_fused_ok(v.lev_n[o[5]], o[6], o[7], 27)) {
-      const int64_t wf = sgnn_conv_bwd_fused_ws(v.lev_n[o[5]], o[6], o[7]);
-      if (wf > w) w = wf;
-    }
-  }
+  if (o[0] == OP_CONV_SUBM) w = sgnn_conv_bwd_weight_ws_bytes(v.lev_n[o[5]], 27, o[6], o[7]);
   if (o[0] == OP_CONV_DOWN) w = sgnn_conv_bwd_weight_ws_bytes(v.lev_n[o[5] + 1], 8, o[6], o[7]);
   if (o[0] == OP_EXPAND)   // partials + the 64 reduced slices themselves (they must not live in the shared gradient arena:
                            // with a deferred lane join the next program's backward pass would overwrite them)
@@ -909,16 +902,11 @@ SGNN_EXPORT int sgnn_prog_backward(const int32_t *ops, const float *opf, int nop
         const int64_t ld_f = down ? lev_ld[lev + 1] : lev_ld[lev];
         const int32_t *tab_b = (const int32_t *)(down ? lev_ptable[lev] : lev_nbr[lev]);
         const int flags_b = down ? SGNN_CONV_TRANSPOSE_W : (SGNN_CONV_TRANSPOSE_W | SGNN_CONV_FLIP_K);
-        // dX and dW from ONE kernel on the training stream where the shape allows and sgnn_tune.conv_bwd_fused asks for it
-        // (conv_bwd_fused.hip; its reduce runs on the training stream too): no lane fork.  Otherwise the lane forks HERE, in
-        // front of the data-gradient launch: the weight gradient runs beside the dX kernel of its layer.
+        // The lane forks HERE, in front of the data-gradient launch: the weight gradient runs beside the dX kernel of its layer.
         // (Never make the lane wait for a LATER kernel of the training stream: one such edge per program — no kernel moved —
         //  costs a replayed step +0.75 ms, profiles/r06l_ab_endfork.txt; every variant of round 3-6 that re-timed the forks lost
         //  0.8-0.9 ms the same way.)
-        bool fused_bwd = false;
-        const bool fused_try = !down && wants(in0) && g_fuse && n > 0 &&
-                               sgnn_conv_epi_supported(cout, cin) && sgnn_conv_bwd_fused_ok(n, cin, cout, K);
-        hipStream_t lane = fused_try ? hs : dw_lane();
+        hipStream_t lane = dw_lane();
         if (wants(in0)) {
           if (g_fuse && sgnn_conv_epi_supported(cout, cin) && n > 0) {
             // the data gradient lands in G(in0) directly: what the buffer (or its alias) already holds is added in the
@@ -947,14 +935,8 @@ SGNN_EXPORT int sgnn_prog_backward(const int32_t *ops, const float *opf, int nop
             epi.ldx = ld_dy;
             epi.ldy = LD(in0);
             epi.n_dev = CNT(lev);
-            fused_bwd = fused_try && sgnn_conv_bwd_fused_usable(n, cin, cout, K, epi, G(in0), X(in0), LD(in0));
-            if (fused_bwd) {
-              PROG_TRY(sgnn_conv_bwd_fused_impl(dy, n, cout, P(par), tab_b, lev_ld[lev], cin, G(in0), epi, X(in0), LD(in0),
-                                                PG(par), dw_base + dw_off, dw_slice(v, i), stream));
-            } else {
-              PROG_TRY(sgnn_conv_fwd_impl(dy, n_dy, cout, P(par), K, tab_b, lev_ld[lev], n, cin, G(in0), flags_b, 0, nullptr,
-                                          nullptr, 1, 1, K, &epi, stream));
-            }
+            PROG_TRY(sgnn_conv_fwd_impl(dy, n_dy, cout, P(par), K, tab_b, lev_ld[lev], n, cin, G(in0), flags_b, 0, nullptr,
+                                        nullptr, 1, 1, K, &epi, stream));
             init[in0] = 1;
             alias[in0] = -1;
           } else {
@@ -967,13 +949,10 @@ SGNN_EXPORT int sgnn_prog_backward(const int32_t *ops, const float *opf, int nop
             PROG_TRY(commit(in0, t));
           }
         }
-        if (!fused_bwd) {
-          if (fused_try) lane = dw_lane();      // (strides the fused kernel does not take: fork late)
-          PROG_TRY(sgnn_conv_bwd_weight_impl(X(in0), n, cin, LD(in0), dy, cout, ld_dy, tab_f, ld_f, K, n_dy, PG(par), 0,
-                                             nullptr, nullptr, 1, 1, K, dw_base + dw_off, dw_slice(v, i),
-                                             (sgnn_stream_t)lane, CNT(down ? lev + 1 : lev)));
-          if (lane != hs) sgnn_stamp("dw>", (sgnn_stream_t)lane);      // (nothing unless stamps are on: scripts/lane_stamps.py)
-        }
+        PROG_TRY(sgnn_conv_bwd_weight_impl(X(in0), n, cin, LD(in0), dy, cout, ld_dy, tab_f, ld_f, K, n_dy, PG(par), 0, nullptr,
+                                           nullptr, 1, 1, K, dw_base + dw_off, dw_slice(v, i), (sgnn_stream_t)lane,
+                                           CNT(down ? lev + 1 : lev)));
+        if (lane != hs) sgnn_stamp("dw>", (sgnn_stream_t)lane);      // (nothing unless stamps are on: scripts/lane_stamps.py)
         dw_off += dw_slice(v, i);
         break;
       }

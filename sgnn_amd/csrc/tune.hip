@@ -13,9 +13,6 @@ sgnn_tune g_tune = {
     /* conv_wide_epi       */ 1,
     /* conv_dw_blocks      */ 256,
     /* conv_dw_c1          */ 1,
-    /* conv_bwd_fused      */ 0,
-    /* conv_bwd_fused_rows */ 40960,
-    /* rulebook_lds        */ 0,
     /* rulebook_multi      */ 1,
     /* scan_inline         */ 1,
     /* chain_merged        */ 1,
@@ -40,9 +37,6 @@ const Field kFields[] = {
     {"conv_wide_epi", &sgnn_tune::conv_wide_epi, 0, 1, true},
     {"conv_dw_blocks", &sgnn_tune::conv_dw_blocks, 1, 4096, false},
     {"conv_dw_c1", &sgnn_tune::conv_dw_c1, 0, 1, true},
-    {"conv_bwd_fused", &sgnn_tune::conv_bwd_fused, 0, 1, true},
-    {"conv_bwd_fused_rows", &sgnn_tune::conv_bwd_fused_rows, 256, (int64_t)1 << 36, false},
-    {"rulebook_lds", &sgnn_tune::rulebook_lds, 0, 1, true},
     {"rulebook_multi", &sgnn_tune::rulebook_multi, 0, 1, true},
     {"scan_inline", &sgnn_tune::scan_inline, 0, 1, true},
     {"chain_merged", &sgnn_tune::chain_merged, 0, 1, true},

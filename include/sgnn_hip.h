@@ -708,6 +708,37 @@ int sgnn_fuse_emit_rows(const float *sdf, int dx, int dy, float voxel_size, cons
 int sgnn_fuse_known(const float *sdf, int64_t n, float voxel_size, uint8_t *known, sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Training chunks cut from a fused scan pair (sgnn_amd.chunks; rules in INTEGRATION.md "Training chunks"): window
+ * scores, and the collated batch of B crops of an input volume and a target pyramid, without .sdfs files.
+ * Volumes are the dense (dz, dy, dx) f32 arrays of the fusion above.  origins: device int32 (nb, 3) = z, y, x of each
+ * crop in FINE voxels; crop extents (cz, cy, cx) are in voxels of the level at hand, cx a multiple of 4.  A window
+ * may reach past the volume: out there nothing is read, the input has no sites, dense values are -inf, known is 255.
+ * ------------------------------------------------------------------------- */
+/* table[w] = {voxels of the window with |sdf_target / vs| < truncation, voxels with |sdf_input| <= keep_abs and
+ * |sdf_input / vs| < truncation} (int32 pairs), window w = (wz * nwy + wy) * nwx + wx at origin (wz*sz, wy*sy, wx*sx)
+ * with extent (cz, cy, cx); extents and strides are multiples of 8.  bricks: workspace of
+ * 2 * ceil(dz/8) * ceil(dy/8) * ceil(dx/8) int32 (the per-brick counts, summed into windows by a second kernel).
+ * Integer sums only: the table is exact and does not depend on any order. */
+int sgnn_chunk_score(const float *sdf_target, const float *sdf_input, int dx, int dy, int dz, float voxel_size,
+                     float truncation, float keep_abs, int cz, int cy, int cx, int sz, int sy, int sx, int nwz, int nwy,
+                     int nwx, int32_t *bricks, int32_t *table, sgnn_stream_t stream);
+/* mask[((b * cz + z) * cy + y) * cx + x] = voxel origin_b + (z, y, x) is inside the volume and |sdf| <= keep_abs and
+ * |sdf / voxel_size| < truncation (the filters of sgnn_fuse_flag) */
+int sgnn_chunk_flag(const float *sdf, int dx, int dy, int dz, const int32_t *origins, int nb, int cz, int cy, int cx,
+                    float keep_abs, float truncation, float voxel_size, uint8_t *mask, sgnn_stream_t stream);
+/* rows q < *count (sel from sgnn_compact_mask of that mask): locs[q] = {z, y, x, b} int64 relative to the crop origin,
+ * feats[q] = sdf / voxel_size */
+int sgnn_chunk_emit_rows(const float *sdf, int dx, int dy, int dz, const int32_t *origins, int nb, int cz, int cy,
+                         int cx, float voxel_size, const int32_t *sel, const int64_t *count, int64_t n_max,
+                         int64_t *locs, float *feats, sgnn_stream_t stream);
+/* out (nb, cz, cy, cx) f32 = (sdf / 2^shift) / voxel_size where |sdf| <= keep_abs, else -inf, read from a volume of
+ * pyramid level `shift` at origin_b >> shift; voxel_size is the FINE voxel size (the divisor of the file loaders).
+ * known (nb, cz, cy, cx) u8 or NULL: the .knw codes of sgnn_fuse_known at voxel_size, 255 outside the volume.
+ * One launch for all nb crops. */
+int sgnn_chunk_crop(const float *sdf, int dx, int dy, int dz, const int32_t *origins, int nb, int cz, int cy, int cx,
+                    int shift, float keep_abs, float voxel_size, float *out, uint8_t *known, sgnn_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Evaluation metrics on the device.
  * ------------------------------------------------------------------------- */
 /* IoU ingredients of one hierarchy level (torch/loss.py:84-120 compute_iou_sparse_dense, fed as in

@@ -132,6 +132,14 @@ PROTOTYPES = {
     'sgnn_fuse_emit_block': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     'sgnn_fuse_emit_rows': (c_i32, [c_vp, c_i32, c_i32, c_f32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     'sgnn_fuse_known': (c_i32, [c_vp, c_i64, c_f32, c_vp, c_vp]),
+    'sgnn_chunk_score': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                 c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    'sgnn_chunk_flag': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_vp,
+                                c_vp]),
+    'sgnn_chunk_emit_rows': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp,
+                                     c_i64, c_vp, c_vp, c_vp]),
+    'sgnn_chunk_crop': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_vp,
+                                c_vp, c_vp]),
     'sgnn_iou_counts': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'sgnn_l1_tgtsurf_ws_bytes': (c_i64, []),
     'sgnn_l1_tgtsurf': (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp, c_i64, c_vp]),

@@ -216,6 +216,19 @@ __device__ __forceinline__ int32_t sgnn_hash_find(const uint64_t *__restrict__ k
 }
 
 // ---------------------------------------------------------------------------
+// the .knw code of one voxel (fusion.hip k_fuse_known, chunks.hip k_chunk_crop; both built with -ffp-contract=off)
+// ---------------------------------------------------------------------------
+// sdf < -vs: max(2, min(255, (int)(-sdf/vs) + 1)); sdf <= vs: 1; else 0.  A never-observed voxel (-inf) gets 2: the
+// reference converts -(-inf)/vs to int, which is undefined in C++ and gives INT_MIN on x86 (so max(2, ..) = 2).
+__device__ __forceinline__ uint8_t sgnn_known_code(float s, float vs) {
+  if (s < -vs) {
+    const float q = __fdiv_rn(-s, vs);
+    return !(q < 2147483648.0f) ? 2 : (uint8_t)max(2, min(255, (int)q + 1));
+  }
+  return s <= vs ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------
 // wave64 / block prefix sums over a 0/1 flag (ballot + popcount)
 // ---------------------------------------------------------------------------
 // Exclusive rank of `flag` among the 256 threads of the block and the block total.

@@ -209,21 +209,11 @@ __global__ __launch_bounds__(256) void k_fuse_emit_rows(const float *__restrict_
   }
 }
 
-// sdf < -vs: max(2, min(255, (int)(-sdf/vs) + 1)); sdf <= vs: 1; else 0.  A never-observed voxel (-inf) gets 2: the
-// reference converts -(-inf)/vs to int, which is undefined in C++ and gives INT_MIN on x86 (so max(2, ..) = 2).
 __global__ __launch_bounds__(256) void k_fuse_known(const float *__restrict__ sdf, int64_t n, float vs,
                                                    uint8_t *__restrict__ known) {
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < n; v += stride) {
-    const float s = sdf[v];
-    uint8_t code;
-    if (s < -vs) {
-      const float q = __fdiv_rn(-s, vs);
-      code = !(q < 2147483648.0f) ? 2 : (uint8_t)max(2, min(255, (int)q + 1));
-    } else {
-      code = s <= vs ? 1 : 0;
-    }
-    known[v] = code;
+    known[v] = sgnn_known_code(sdf[v], vs);
   }
 }
 

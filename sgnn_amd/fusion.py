@@ -280,6 +280,64 @@ class TSDFVolume(object):
                           vals.cpu().numpy(), self.known().cpu().numpy() if known else None)
 
 
+def level_transform(level):
+    """S_k (4x4, fp64) of pyramid level k, factor f = 2**k: fine voxel coordinates g0 -> (g0 - (f-1)/2) / f, the
+    coordinates of the level whose voxel c is centred on the f**3 fine voxels f*c .. f*c + f-1 it covers."""
+    f = float(2 ** int(level))
+    s = np.eye(4, dtype=np.float64)
+    s[:3, :3] /= f
+    s[:3, 3] = -(f - 1.0) / (2.0 * f)
+    return s
+
+
+class TSDFPyramid(object):
+    """The same frames fused at 1x, 2x, 4x, ... the voxel size: `levels` TSDFVolumes, the target hierarchy of a
+    training chunk (chunks.ChunkCutter).  Host plumbing over the existing kernels: every level is an ordinary
+    TSDFVolume and integrate() calls each level's integrate; there is no pyramid kernel.
+
+    Level k (factor f = 2**k) has dims ceil(d / f), voxel size f * voxel_size (fp32 product) and world2grid_k =
+    level_transform(k) @ world2grid, formed in fp64 from the fp32 world2grid that level 0 holds and rounded once to
+    fp32.  An obb (a, e0, e1, e2 in fine voxel coordinates) is carried along: corner through S_k, edges / f, in fp64,
+    rounded to fp32.  The integration kernel truncates at 3 voxel sizes of the volume it is given, so every level's
+    band is three of its own voxels; a level-f value divided by f and by the fine voxel size (what the .sdfs route
+    does) is the distance in level-f voxels, the convention of synth.block_arrays."""
+
+    def __init__(self, dims_xyz, voxel_size, world2grid, levels=4, obb=None, **volume_kwargs):
+        if int(levels) < 1:
+            raise ValueError('a pyramid needs at least one level')
+        w2g = _host(world2grid, np.float32).reshape(4, 4).astype(np.float64)
+        vs = np.float32(voxel_size)
+        self.volumes = []
+        for k in range(int(levels)):
+            f = 2 ** k
+            s = level_transform(k)
+            o = None
+            if obb is not None:
+                o64 = _host(obb, np.float64).reshape(4, 3)
+                o = np.concatenate([o64[:1] @ s[:3, :3].T + s[:3, 3], o64[1:] / f]).astype(np.float32)
+            self.volumes.append(TSDFVolume([-(-int(d) // f) for d in dims_xyz], np.float32(f) * vs,
+                                           (s @ w2g).astype(np.float32), obb=o, **volume_kwargs))
+
+    def __len__(self):
+        return len(self.volumes)
+
+    def __getitem__(self, k):
+        return self.volumes[k]
+
+    def integrate(self, depth, intrinsics, cam2world, chunk=None):
+        """TSDFVolume.integrate on every level (the depth stack is moved to the device once)."""
+        d = _to_device(depth, torch.float32, self.volumes[0].device)
+        for v in self.volumes:
+            v.integrate(d, intrinsics, cam2world, chunk)
+        return self
+
+    def copy(self):
+        """An independent snapshot of every level."""
+        c = TSDFPyramid.__new__(TSDFPyramid)
+        c.volumes = [v.copy() for v in self.volumes]
+        return c
+
+
 def write_scan(path_sdf, dims_zyx, voxel_size, world2grid, locs_xyz, vals, known=None):
     """Host arrays -> the .sdf (data.write_scene: (x, y, z) u32 + metric sdf) and, given known (dz, dy, dx) u8, the
     .knw next to it (data.write_known)."""

@@ -739,6 +739,27 @@ int sgnn_chunk_crop(const float *sdf, int dx, int dy, int dz, const int32_t *ori
                     int shift, float keep_abs, float voxel_size, float *out, uint8_t *known, sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Depth frames rendered from a triangle mesh (sgnn_amd.render; rules in INTEGRATION.md section F): the virtual-scan
+ * source of datagen/GenerateScans (Scene.cpp:107-158).  The output is what sgnn_fuse_bilateral / sgnn_fuse_integrate
+ * take: one (nframes, h, w) f32 stack in metres, -inf = nothing seen.
+ * ------------------------------------------------------------------------- */
+/* one frame of sgnn_render_depth (64 bytes; the frame table is a device array of these) */
+typedef struct sgnn_render_frame {
+  float m[12];   /* rows 0..2 of inv(cam2world): world (x,y,z,1) -> camera, fp32; NaN = non-finite pose, empty frame */
+  float intr[4]; /* fx, fy, cx, cy */
+} sgnn_render_frame;
+/* verts (nverts, 3) f32 world metres, faces (ntri, 3) i32, out (nframes, h, w) f32, 16-byte aligned; the output is
+ * the depth buffer while the call runs.  chunk: frames per triangle launch (<= 0: all), wave_pixels: pixel boxes
+ * above it are rasterised by a whole wave (<= 0: the built-in constant); the result depends on neither.  A face
+ * with an index outside [0, nverts) is not drawn and, with status != NULL, raises SGNN_STATUS_COORD_RANGE there.
+ * counters: NULL, or device int64[3] that the call adds to (measurements and tests): triangles drawn by one lane,
+ * triangles drawn by a wave, covered pixels (= atomic minima issued).  h, w <= 16384; ntri * 3 and
+ * nframes * h * w < 2^31. */
+int sgnn_render_depth(const float *verts, int nverts, const int32_t *faces, int ntri, const sgnn_render_frame *frames,
+                      int nframes, int chunk, int h, int w, float z_clip, float depth_min, float depth_max,
+                      int wave_pixels, float *out, int32_t *status, int64_t *counters, sgnn_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Evaluation metrics on the device.
  * ------------------------------------------------------------------------- */
 /* IoU ingredients of one hierarchy level (torch/loss.py:84-120 compute_iou_sparse_dense, fed as in

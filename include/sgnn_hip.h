@@ -545,6 +545,14 @@ int64_t sgnn_prog_arena_floats(const int32_t *ops, int nops, const int32_t *bufs
 int64_t sgnn_prog_ws_bytes(const int32_t *ops, int nops, const int64_t *lev_n, int nlev);
 int64_t sgnn_prog_buffer_offset(const int32_t *ops, int nops, const int32_t *bufs, int nbuf, int n_ext,
                                 const int64_t *lev_n, int nlev, const int32_t *keep, int infer, int b);
+/* What the executor decides for these descriptors under the current sgnn_tune switches (tests, diagnostics): host only,
+ * launches nothing, takes no stream.  mode as in sgnn_prog_arena_floats (3: the plan of the bf16 layout).
+ * out int32[4 * nops + 3 * nbuf]: per op {skip (the forward pass launches nothing for it), add_dst (>= 0: the
+ * convolution stores the sum of the AddTable behind it into that buffer), join_view (the JoinTable is in place),
+ * lin_bn (>= 0: the head's data gradient is formed inside the backward pass of that BatchNorm op)}, then per buffer
+ * {root (the buffer whose storage it lives in), col (its column offset there), ld (its row stride in elements)}. */
+int sgnn_prog_plan(const int32_t *ops, int nops, const int32_t *bufs, int nbuf, int n_ext, const int64_t *lev_n,
+                   int nlev, const int32_t *keep, int mode, int32_t *out);
 /* training: 0 = eval, 1 = training (batch statistics), | 2 = inference layout (see sgnn_prog_arena_floats mode 2),
  * | 4 = bf16 storage (mode 3; only as 2 | 4, eval: running statistics).  In the bf16 layout the externals stay fp32,
  * every arena buffer is bf16 except the LINEAR outputs (fp32 logits); math is fp32 with one rounding per stored value.

@@ -501,6 +501,30 @@ SGNN_EXPORT int64_t sgnn_prog_buffer_offset(const int32_t *ops, int nops, const 
   return P.root[b] == b ? L.buf_off[b] : -1;      // buffers the caller keeps are never views
 }
 
+// What make_plan decides for these descriptors under the current switches, for tests and diagnostics: host only, nothing
+// is launched.  mode as in sgnn_prog_arena_floats (3: the plan of the bf16 layout).  out: int32[4 * nops + 3 * nbuf] =
+// per op {skip, add_dst, join_view, lin_bn}, then per buffer {root, col, ld}.
+SGNN_EXPORT int sgnn_prog_plan(const int32_t *ops, int nops, const int32_t *bufs, int nbuf, int n_ext, const int64_t *lev_n,
+                               int nlev, const int32_t *keep, int mode, int32_t *out) {
+  SGNN_CHECK_ARG(ops && bufs && lev_n && out && nops >= 0 && nbuf >= 1 && nlev >= 1 && n_ext >= 0 && n_ext <= nbuf &&
+                 mode >= 0 && mode <= 3);
+  View v{ops, nullptr, nops, bufs, nbuf, n_ext, lev_n, nullptr, nullptr, nullptr, nullptr, nullptr, nlev};
+  Plan P;
+  make_plan(v, keep, P, mode == 3);
+  for (int i = 0; i < nops; ++i) {
+    out[4 * i] = P.skip[i];
+    out[4 * i + 1] = P.add_dst[i];
+    out[4 * i + 2] = P.join_view[i];
+    out[4 * i + 3] = P.lin_bn[i];
+  }
+  for (int b = 0; b < nbuf; ++b) {
+    out[4 * nops + 3 * b] = P.root[b];
+    out[4 * nops + 3 * b + 1] = P.col[b];
+    out[4 * nops + 3 * b + 2] = (int32_t)P.ld[b];
+  }
+  return SGNN_OK;
+}
+
 // The forward pass of the bf16 inference layout (training = 2 | 4; infer_bf16.hip): the same plan — fused conv ->
 // AddTable, in-place JoinTable views — over bf16 rows (row strides rounded up to 8 elements).  Externals stay the
 // caller's fp32 tensors: CONCAT_IN converts while it gathers, any other reader gets a bf16 shadow copy made in front of

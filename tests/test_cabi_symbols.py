@@ -21,7 +21,7 @@ def test_header_declares_the_expected_surface():
     names = declared_functions()
     for must in ['sgnn_hash_build', 'sgnn_rulebook_subm3', 'sgnn_rulebook_down2', 'sgnn_conv_fwd',
                  'sgnn_conv_bwd_weight', 'sgnn_bn_fwd', 'sgnn_bn_bwd', 'sgnn_compact_sigmoid', 'sgnn_expand8_coords',
-                 'sgnn_hash_lookup', 'sgnn_concat_rows', 'sgnn_sparse_to_dense', 'sgnn_linear_fwd']:
+                 'sgnn_hash_lookup', 'sgnn_concat_rows', 'sgnn_sparse_to_dense', 'sgnn_linear_fwd', 'sgnn_prog_plan']:
         assert must in names
 
 

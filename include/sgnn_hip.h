@@ -768,6 +768,37 @@ int sgnn_render_depth(const float *verts, int nverts, const int32_t *faces, int 
                       int wave_pixels, float *out, int32_t *status, int64_t *counters, sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Mesh-to-mesh distances (sgnn_amd.meshdist; rules in INTEGRATION.md section G): the exact nearest triangle of a
+ * mesh for many query points through a uniform grid of triangle lists, and area-weighted surface samples.
+ *   sgnn_meshdist_pack   -> records (ntri, 12) f32: a, ab, ac as three 16-byte rows (w = 0); boxes (ntri, 6) f32:
+ *                           min and max corner of the face; usable (ntri) u8.  A face that rule 1 ignores gets the
+ *                           box (+inf, -inf), which the passes below skip.  An index outside [0, nverts) makes the
+ *                           face unusable and, with status != NULL, raises SGNN_STATUS_COORD_RANGE there.
+ *   sgnn_meshdist_count  -> counts[cell] += faces whose box touches the cell (the caller zeroes counts)
+ *   (caller: offsets = exclusive scan of counts, nx*ny*nz + 1 entries, i32; the total must stay below 2^31)
+ *   sgnn_meshdist_fill   -> refs[offsets[cell] + k] = face, k from the zeroed cursor array; order inside a list is
+ *                           arbitrary and does not show in any result
+ *   sgnn_meshdist_query  -> dist (npts) f32 and face (npts) i32 by the shell walk of rule 5; max_dist = +inf for an
+ *                           unbounded query.  counters: NULL, or device int64[2] that the call adds to: cells
+ *                           visited, (point, face) pairs evaluated.
+ *   sgnn_mesh_sample     -> pts (n, 3) f32 and fid (n) i32 of rule 6 from the records and the fp64 cumulative areas
+ *                           cum (ntri); last_usable = the face a search past the end is clamped to.
+ * The grid is lo (3 floats), hi (3 floats, query only), pitch cell > 0 and nx, ny, nz cells, nx*ny*nz < 2^31.
+ * ------------------------------------------------------------------------- */
+int sgnn_meshdist_pack(const float *verts, int nverts, const int32_t *faces, int ntri, float *records, float *boxes,
+                       uint8_t *usable, int32_t *status, sgnn_stream_t stream);
+int sgnn_meshdist_count(const float *boxes, int ntri, float lox, float loy, float loz, float cell, int nx, int ny,
+                        int nz, int32_t *counts, sgnn_stream_t stream);
+int sgnn_meshdist_fill(const float *boxes, int ntri, float lox, float loy, float loz, float cell, int nx, int ny,
+                       int nz, const int32_t *offsets, int32_t *cursor, int32_t *refs, sgnn_stream_t stream);
+int sgnn_meshdist_query(const float *points, int64_t npts, const float *records, const int32_t *offsets,
+                        const int32_t *refs, float lox, float loy, float loz, float hix, float hiy, float hiz,
+                        float cell, int nx, int ny, int nz, float max_dist, float *dist, int32_t *face,
+                        int64_t *counters, sgnn_stream_t stream);
+int sgnn_mesh_sample(const float *records, const double *cum, int ntri, int last_usable, int64_t n, int64_t seed,
+                     float *pts, int32_t *fid, sgnn_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Evaluation metrics on the device.
  * ------------------------------------------------------------------------- */
 /* IoU ingredients of one hierarchy level (torch/loss.py:84-120 compute_iou_sparse_dense, fed as in

@@ -7,6 +7,8 @@ into HIP kernels is row f1 ("next").
 import torch
 import torch.nn.functional as F
 
+from .scn.sites import info
+
 UNK_THRESH = 2
 UNK_ID = -1
 
@@ -83,7 +85,7 @@ def compute_targets_and_weights(target, hierarchy, num_hierarchy_levels, truncat
     ptrs = dict((k, np.ascontiguousarray(np.array(v + [0], dtype=np.uint64))) for k, v in arr.items())
     locs = input_locs.contiguous() if want_w else None
     kn = known.contiguous() if use_loss_masking else None
-    n_cnt = getattr(input_locs, '_sgnn_cnt', None) if want_w else None     # capacity mode: live rows of input_locs
+    n_cnt = info(input_locs).cnt if want_w else None     # capacity mode: live rows of input_locs
     _lib.call('sgnn_loss_targets', _lib.ptr(target), _lib.ptr(kn), _lib.ptr(locs), 0 if locs is None else int(locs.shape[0]),
               _lib.ptr(n_cnt), B, d0, d1, d2, float(truncation), int(bool(use_loss_masking)), float(weight_missing_geo), L - 1,
               ptrs['hin'].ctypes.data, _lib.ptr(tsdf), _lib.ptr(hiers[-1]), _lib.ptr(occs[-1]),
@@ -167,7 +169,7 @@ class _LevelLoss(torch.autograd.Function):
         out2 = torch.empty(2, dtype=torch.float32, device=vals.device)
         wsb = _lib.query('sgnn_loss_ws_bytes')
         ws = rt.workspace(wsb)
-        m_cnt = getattr(locs, '_sgnn_cnt', None)       # capacity mode: live row count (device int64[1])
+        m_cnt = info(locs).cnt     # capacity mode: live row count (device int64[1])
         args = (_lib.ptr(locs), _lib.ptr(vals), vstride, occ_col, sdf_col, _lib.ptr(tgt_occ), _lib.ptr(tgt_sdf),
                 _lib.ptr(weights), _lib.ptr(known), int(dims[0]), int(dims[1]), int(dims[2]), m, int(use_log),
                 mask_mode, _lib.ptr(m_cnt))
@@ -209,7 +211,7 @@ class _TotalLoss(torch.autograd.Function):
         p = lambda t: 0 if t is None else t.data_ptr()
         for l, (lv, v) in enumerate(zip(levels, vals)):
             v = v.contiguous()
-            m_cnt = getattr(lv['locs'], '_sgnn_cnt', None)       # capacity mode: live row count (device int64[1])
+            m_cnt = info(lv['locs']).cnt     # capacity mode: live row count (device int64[1])
             locs = lv['locs'].contiguous()
             dims = lv['tgt_sdf'].shape[2:]
             m, vstride = v.shape

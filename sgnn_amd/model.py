@@ -29,6 +29,7 @@ from . import scn
 from .scn import functions as F_
 from .scn import program as P_
 from .scn.metadata import coords_from_locs
+from .scn.sites import info, attach
 
 
 STAGES = True   # each generative stage (skip join .. heads) as one native program; False: per-module glue
@@ -267,7 +268,7 @@ class _DenseGeometry(object):
     def __init__(self, batch, dims, device):
         self.batch, self.dims, self.device = batch, dims, device
         self.coords = F_.dense_coords(batch, dims[0], dims[1], dims[2], device)
-        self.coords._sgnn_bounds = (int(batch), int(dims[0]), int(dims[1]), int(dims[2]))   # travels to every generated level
+        attach(self.coords, bounds=(int(batch), int(dims[0]), int(dims[1]), int(dims[2])))   # travels to every generated level
         self.grid = scn.Grid(self.coords)
         self._levels = {}
 
@@ -477,11 +478,11 @@ class Refinement(nn.Module):
             return None
         locs = prev[3]
         x0 = self.p0([locs, ext[0]])
-        cnt8 = getattr(locs, '_sgnn_cnt8', None)              # capacity mode: live rows of the 8-child expansion
+        cnt8 = info(locs).cnt8        # capacity mode: live rows of the 8-child expansion
         outs, _, _ = P_.run_program(prog, x0, self.training, [prog.taps[id(self.n2)][0], prog.taps[id(self.linear)][0]],
                                     ext=ext, idx=idx, extra_rows=extra,
                                     extra_cnt=None if cnt8 is None else {'child': cnt8})
-        children = getattr(locs, '_sgnn_children', None)     # already made by GenModel._teacher_plans
+        children = info(locs).children   # already made by GenModel._teacher_plans
         return outs[0], outs[1], (children if children is not None else F_.expand8_coords(locs, with_i64=True))
 
 
@@ -501,7 +502,7 @@ def _stage_program(owner, prev, skip, chain, nf_in, tail):
             return None, None, None, None
         srcs[2] = ('skip', int(feats_from.shape[1]), 1)
         ext.append(feats_from)
-        idx.append(grid_from.lookup(locs, getattr(locs, '_sgnn_cnt', None)))
+        idx.append(grid_from.lookup(locs, info(locs).cnt))
         extra['skip'] = grid_from.n
     cache = owner.__dict__.setdefault('_stage_progs', {})
     key = tuple(srcs)
@@ -632,10 +633,9 @@ class GenModel(nn.Module):
             n = int(coords.shape[0])
             chain = MD.PendingChain(coords, n, False, depth)
             plan = chain.finalize(n, MD.runtime(dev).read_counts())
-            # the level-0 Grid holds a view of `coords`; hanging the plan on `coords` itself would close a reference
-            # cycle through the view's base that the garbage collector cannot see (one leaked pyramid per step)
-            coords = coords[:]
-            coords._sgnn_plan = plan
+            # the level-0 Grid holds a view of `coords`; a record that owns the plan on `coords` itself would close a
+            # reference cycle through the view's base that the garbage collector cannot see (one leaked pyramid per step)
+            coords = attach(coords[:], plan=plan)
         enc = self.encoder
         dims = tuple(int(v) >> depth for v in enc.process_sparse[0].p0.spatial_size)
         plans = self._teacher_plans(dense_geometry(batch_size, dims, dev), self._runs(loss_weights), teacher)
@@ -643,9 +643,9 @@ class GenModel(nn.Module):
 
     def forward(self, x, loss_weights, batch_size=None, teacher=None, geometry=None, capacity=None):
         """capacity (scn.capacity.Capacity, optional; not in the reference): capacity mode — every level's tensors have
-        the plan's capacities, the live row counts stay on the device (results carry them as `_sgnn_cnt`; rows past a
+        the plan's capacities, the live row counts stay on the device (results carry them: scn.sites.info(t).cnt; rows past a
         count are undefined) and the call performs NO host read-back, so a training step can be captured in a HIP
-        graph (train.GraphStep).  x[0] may have more rows than the batch (x[0]._sgnn_cnt or capacity.input_cnt()
+        graph (train.GraphStep).  x[0] may have more rows than the batch (info(x[0]).cnt or capacity.input_cnt()
         holds the live count).  Needs batch_size and the native stage path.
         teacher (optional, not in the reference): list of the L dense target occupancy volumes (loss.compute_targets'
         target_for_occs); when given, every generative mask is `target occupancy == 1` at the candidate site instead of
@@ -658,8 +658,8 @@ class GenModel(nn.Module):
         if capacity is not None:
             if geometry is not None or batch_size is None or not (P_.ENABLED and STAGES):
                 raise ValueError('capacity mode: pass batch_size, no geometry plan, native stage path on')
-            if getattr(x[0], '_sgnn_cnt', None) is None:
-                x[0]._sgnn_cnt = capacity.input_cnt()
+            if info(x[0]).cnt is None:
+                attach(x[0], cnt=capacity.input_cnt())
         x = [coords_from_locs(x[0], x[1].device), x[1]]
         R = len(self.refinement)
         runs = self._runs(loss_weights)
@@ -724,8 +724,9 @@ class GenModel(nn.Module):
                 plans.append(None)
                 continue
             locs = plan[2]
-            locs._sgnn_children = F_.expand8_coords(locs)
-            plan = F_.compact_sigmoid_plan(locs._sgnn_children, 2, 8 * plan[1], locs._sgnn_children,
+            children = F_.expand8_coords(locs)
+            attach(locs, children=children)
+            plan = F_.compact_sigmoid_plan(children, 2, 8 * plan[1], children,
                                            self.refinement[h].plan_depth, teacher[h + 1])
             plans.append(plan)
         return plans

@@ -20,6 +20,8 @@ batch with larger capacities (`grown()`).
 import numpy as np
 import torch
 
+from .sites import info
+
 SLOTS = 64
 ENC0 = 1
 GEN0 = 8
@@ -118,5 +120,5 @@ class Capacity(object):
 
 def trim(t):
     """Rows [0, live count) of a capacity-mode tensor (one read-back per distinct count; not for the training loop)."""
-    cnt = getattr(t, '_sgnn_cnt', None)
+    cnt = info(t).cnt
     return t if cnt is None else t[:int(cnt.item())]

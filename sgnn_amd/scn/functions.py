@@ -9,6 +9,7 @@ from torch.autograd import Function
 from .. import _lib
 from .._lib import ptr
 from .metadata import runtime
+from .sites import info, attach
 
 import os
 
@@ -560,7 +561,7 @@ def compact_sigmoid_plan(logits, stride, n, coords_all, depth, teacher=None):
     """compact_sigmoid + the kept rows' coordinates + the stride-2 pyramid (`depth` levels) below them, with ONE host
     read-back for all row counts: the coordinate gather and the pyramid kernels read the kept-row count from device
     memory (sgnn_gather_rows_dn, sgnn_down2_chain).  Returns (sel[:count], count, locs (count,4) int32); when a
-    pyramid was built, `locs` carries it (`_sgnn_plan`) and the next InputLayer adopts it instead of rebuilding."""
+    pyramid was built, `locs` carries it (sites.info(locs).plan) and the next InputLayer adopts it instead of rebuilding."""
     from . import metadata as MD
     rt = runtime(logits.device)
     if not MD.CHAIN or depth < 1 or n == 0:
@@ -589,21 +590,21 @@ def compact_sigmoid_plan(logits, stride, n, coords_all, depth, teacher=None):
     if MD.COUNT_LOG is not None:
         MD.COUNT_LOG.append(('gen', count, [int(v) for v in host[2:2 + chain.depth]]))
     if count:
-        locs._sgnn_plan = chain.finalize(count, host)
+        attach(locs, plan=chain.finalize(count, host))
     return sel[:count], count, locs
 
 
 def compact_capped(logits, stride, n_all, coords_all, depth, capacity, g, teacher=None):
     """Capacity-mode counterpart of compact_sigmoid_plan for generative level g of `capacity` (scn.capacity.Capacity):
-    no host read-back.  The candidate count is coords_all._sgnn_cnt (None: n_all is exact, the dense coarse volume);
-    returns (sel (n_all), kept capacity K, locs (K,4) int32) where locs carries its live count (`_sgnn_cnt`, and
-    `_sgnn_cnt8` = 8 x it) and, for depth >= 1, the stride-2 pyramid below it (`_sgnn_plan`) sized by the capacities."""
+    no host read-back.  The candidate count is info(coords_all).cnt (None: n_all is exact, the dense coarse volume);
+    returns (sel (n_all), kept capacity K, locs (K,4) int32) where locs carries (scn.sites) its live count `cnt`,
+    `cnt8` = 8 x it and, for depth >= 1, the stride-2 pyramid below it (`plan`) sized by the capacities."""
     from . import metadata as MD
     dev = coords_all.device
     rt = runtime(dev)
     K, pyr_caps = capacity.gen[g]
     cnt2 = capacity.kept2(g)
-    n_cnt = getattr(coords_all, '_sgnn_cnt', None)
+    n_cnt = info(coords_all).cnt
     sel = torch.empty(max(n_all, 1), dtype=torch.int32, device=dev)
     wsb = _lib.query('sgnn_compact_ws_bytes', n_all)
     ws = rt.workspace(wsb)
@@ -626,12 +627,12 @@ def compact_capped(logits, stride, n_all, coords_all, depth, capacity, g, teache
             _lib.call('sgnn_compact_dense_cap', ptr(coords_all), n_all, ptr(n_cnt), ptr(teacher), B, d0, d1, d2, ptr(sel),
                       ptr(cnt2), K, ptr(rt.status32), ptr(ws), wsb)
         _lib.call('sgnn_gather_rows_dn', ptr(coords_all), 4, ptr(sel), ptr(kept), K, ptr(locs))
-    locs._sgnn_cnt, locs._sgnn_cnt8 = kept, kept8
+    attach(locs, cnt=kept, cnt8=kept8)
     if depth >= 1:
         depth = min(depth, len(pyr_caps))
         chain = MD.PendingChain(locs, K, True, depth, n0_cnt=kept, counts=capacity.pyr_counts(g, depth),
                                 level_caps=pyr_caps)
-        locs._sgnn_plan = chain.finalize_capped()
+        attach(locs, plan=chain.finalize_capped())
     return sel, K, locs
 
 
@@ -648,9 +649,9 @@ def compact_mask(mask_u8, n):
 def _inherit_bounds(coords, parent, scale=1):
     """A subset (scale = 1) or the 8-child expansion (scale = 2) of sites that lie in [0, Z) x [0, Y) x [0, X), b < B by
     construction does so too: the bound travels with the coordinates (Grid.bounds: such a level needs no hash grid)."""
-    b = getattr(parent, '_sgnn_bounds', None)
+    b = info(parent).bounds
     if b is not None:
-        coords._sgnn_bounds = (int(b[0]), int(b[1]) * scale, int(b[2]) * scale, int(b[3]) * scale)
+        attach(coords, bounds=(int(b[0]), int(b[1]) * scale, int(b[2]) * scale, int(b[3]) * scale))
     return coords
 
 
@@ -663,20 +664,20 @@ def gather_coords(coords32, sel, m):
 
 def expand8_coords(coords32, with_i64=False):
     """with_i64: the children's int64 rows (what coords_to_i64 would return for them) are written in the same pass and
-    travel with the result (`_sgnn_i64`) — the model returns them as the level's `locs`."""
+    travel with the result (sites.info(out).i64) — the model returns them as the level's `locs`."""
     n = coords32.shape[0]
     out = torch.empty(8 * n, 4, dtype=torch.int32, device=coords32.device)
-    cnt = getattr(coords32, '_sgnn_cnt', None)
+    parent = info(coords32)
+    cnt, o64 = parent.cnt, None
     if with_i64 and FUSED_GLUE:
         o64 = torch.empty(8 * n, 4, dtype=torch.int64, device=coords32.device)
         _lib.call('sgnn_expand8_coords_i64', ptr(coords32), n, ptr(out), ptr(o64), ptr(cnt))
-        out._sgnn_i64 = o64
+        attach(out, i64=o64)
     else:
         _lib.call('sgnn_expand8_coords', ptr(coords32), n, ptr(out), ptr(cnt))
     if cnt is not None:          # capacity mode: the children's live row count (8 x kept) sits next to the kept count
-        out._sgnn_cnt = coords32._sgnn_cnt8
-        if getattr(out, '_sgnn_i64', None) is not None:
-            out._sgnn_i64._sgnn_cnt = out._sgnn_cnt
+        for t in (out,) if o64 is None else (out, o64):
+            attach(t, cnt=parent.cnt8)
     return _inherit_bounds(out, coords32, 2)
 
 
@@ -687,13 +688,11 @@ def dense_coords(batch, d0, d1, d2, device):
 
 
 def coords_to_i64(coords32):
-    made = getattr(coords32, '_sgnn_i64', None)       # expand8_coords(with_i64=True) already wrote them
+    made = info(coords32).i64       # expand8_coords(with_i64=True) already wrote them
     if made is not None:
         return made
     n = coords32.shape[0]
     out = torch.empty(n, 4, dtype=torch.int64, device=coords32.device)
-    cnt = getattr(coords32, '_sgnn_cnt', None)
+    cnt = info(coords32).cnt
     _lib.call('sgnn_coords_to_i64', ptr(coords32), n, ptr(out), ptr(cnt))
-    if cnt is not None:
-        out._sgnn_cnt = cnt
-    return out
+    return out if cnt is None else attach(out, cnt=cnt)

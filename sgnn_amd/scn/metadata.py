@@ -14,6 +14,7 @@ import torch
 
 from .. import _lib
 from .._lib import ptr
+from .sites import info, attach, carry
 
 
 SIDE_LANE = os.environ.get('SGNN_SIDE_LANE', '1') != '0'     # run dW on a second stream during program backward (sgnn_prog_set_side_stream)
@@ -201,7 +202,7 @@ class Grid(object):
         self.dims = None       # spatial size (z, y, x) of the level once a Metadata registers the grid
         # (B, Z, Y, X): every site satisfies b < B, z < Z, ... BY CONSTRUCTION (generated levels: children of a dense coarse
         # volume; the model passes the bound along with the coordinates) — such a level's rulebook needs no hash grid
-        self.bounds = getattr(coords32, '_sgnn_bounds', None)
+        self.bounds = info(coords32).bounds
         self.ld = _round_up(max(self.n, 1), 256)   # table leading dimension (conv kernels: multiple of 256)
 
     def hash(self):
@@ -253,9 +254,7 @@ class Grid(object):
     def locations_i64(self):
         out = torch.empty(self.n, 4, dtype=torch.int64, device=self.device)
         _lib.call('sgnn_coords_to_i64', ptr(self.coords), self.n, ptr(out), ptr(self.cnt))
-        if self.cnt is not None:
-            out._sgnn_cnt = self.cnt
-        return out
+        return out if self.cnt is None else attach(out, cnt=self.cnt)
 
 
 class Down2(object):
@@ -358,7 +357,7 @@ class PendingChain(object):
         """-> (grid of level 0, [Down2 level l -> l+1])."""
         counts = [int(v) for v in host_state[2:2 + self.depth]]
         fine = Grid(self.coords_cap[:n0])
-        fine.bounds = getattr(self.coords_cap, '_sgnn_bounds', None)
+        fine.bounds = info(self.coords_cap).bounds
         grid0, downs = fine, []
         for l in range(self.depth):
             nc = counts[l]
@@ -506,7 +505,7 @@ def join_pyramid_lane(device):
 def coords_from_locs(locs, device):
     """Reference-style LongTensor (N,4) [z,y,x,b] (any device) -> device int32 rows."""
     rt = runtime(device)
-    cnt = getattr(locs, '_sgnn_cnt', None)       # capacity mode: live row count of `locs` (device int64[1])
+    cnt = info(locs).cnt     # capacity mode: live row count of `locs` (device int64[1])
     if locs.dtype == torch.int32:
         out = locs.to(device).contiguous()
     else:
@@ -514,9 +513,6 @@ def coords_from_locs(locs, device):
         n = int(src.shape[0])
         out = torch.empty(n, 4, dtype=torch.int32, device=device)
         _lib.call('sgnn_coords_from_i64', ptr(src), n, ptr(out), ptr(rt.status32), ptr(cnt))
-    if cnt is not None and out is not locs:
-        out._sgnn_cnt = cnt
-        for a in ('_sgnn_cnt8', '_sgnn_plan', '_sgnn_children'):
-            if hasattr(locs, a):
-                setattr(out, a, getattr(locs, a))
+    if cnt is not None:        # what the stages read next to the coordinates; neither the bound nor the int64 rows
+        carry(out, locs, 'cnt', 'cnt8', 'plan', 'children')
     return out

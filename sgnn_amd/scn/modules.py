@@ -7,6 +7,7 @@ import torch.nn as nn
 
 from .metadata import Metadata, Grid, coords_from_locs
 from . import functions as F_
+from .sites import info
 
 
 class SparseConvNetTensor(object):
@@ -115,12 +116,12 @@ class InputLayer(nn.Module):
         coords = coords_from_locs(locs, feats.device)
         md = Metadata(self.dimension)
         key = tuple(int(v) for v in self.spatial_size)
-        plan = getattr(coords, '_sgnn_plan', None)   # stride-2 pyramid pre-built with the compaction that made coords
+        plan = info(coords).plan   # stride-2 pyramid pre-built with the compaction that made coords
         if plan is not None and plan[0].n == coords.shape[0]:
             g = plan[0]
             md.adopt(key, g, plan[1])
         else:
-            g = Grid(coords, cnt=getattr(coords, '_sgnn_cnt', None))   # capacity mode: the live row count travels along
+            g = Grid(coords, cnt=info(coords).cnt)   # capacity mode: the live row count travels along
             md.set_input(key, g)
         return SparseConvNetTensor(feats, md, key, g)
 

@@ -13,6 +13,7 @@ import torch
 import torch.distributed as dist
 
 from . import loss as loss_util
+from .scn.sites import attach, carry
 
 
 def _parse_cpulist(text):
@@ -703,17 +704,11 @@ class GraphStep(object):
     # -- pieces --------------------------------------------------------------------------------------------
     @staticmethod
     def _detached(out_sdf, out_occs):
-        """The model's outputs without their autograd graph (same storage, live-count attribute kept).  A caller that holds
+        """The model's outputs without their autograd graph (same storage, live counts kept).  A caller that holds
         the graph of an earlier step across a capturing call makes autograd re-use AccumulateGrad nodes created on another
         stream — a cross-stream synchronisation inside the capture, which HIP answers with a crash in hipStreamEndCapture."""
         def d(t):
-            if not torch.is_tensor(t):
-                return t
-            u = t.detach()
-            for a in ('_sgnn_cnt', '_sgnn_cnt8'):
-                if hasattr(t, a):
-                    setattr(u, a, getattr(t, a))
-            return u
+            return carry(t.detach(), t, 'cnt', 'cnt8') if torch.is_tensor(t) else t
         return [d(t) for t in out_sdf], [[d(t) for t in o] for o in out_occs]
 
     def _teacher(self, toccs):
@@ -786,7 +781,7 @@ class GraphStep(object):
               'sdf': torch.empty_like(batch['sdf']),
               'known': torch.empty_like(batch['known']) if batch.get('known') is not None else None,
               'hierarchy': [torch.empty_like(h) for h in (batch.get('hierarchy') or [])]}
-        st['locs']._sgnn_cnt = cap.input_cnt()
+        attach(st['locs'], cnt=cap.input_cnt())
         self.static = st
 
     def buffers(self):

@@ -46,12 +46,13 @@ def _classic(model, batch, lw):
 
 def _capped(model, batch, lw, cap):
     from sgnn_amd import loss as L
+    from sgnn_amd.scn.sites import attach
     locs, feats = batch['input']
     n = int(locs.shape[0])
     slocs = torch.zeros(cap.input_rows, 4, dtype=torch.int64, device='cuda')
     sfeats = torch.zeros(cap.input_rows, feats.shape[1], device='cuda')
     slocs[:n], sfeats[:n] = locs, feats
-    slocs._sgnn_cnt = cap.input_cnt()
+    attach(slocs, cnt=cap.input_cnt())
     cap.set_input_rows(n)
     (tsdf, toccs, thier), w = L.compute_targets_and_weights(batch['sdf'], batch['hierarchy'], 4, 3.0, True, batch['known'], 5.0,
                                                             slocs)
@@ -118,6 +119,46 @@ def test_capacity_forward_backward_equals_the_classic_path():
         assert float((pa.grad - pb.grad).abs().max()) <= lim, (na, float((pa.grad - pb.grad).abs().max()), scale)
     for (na, ba), (nb, bb) in zip(ma.named_buffers(), mb.named_buffers()):
         assert torch.allclose(ba.float(), bb.float(), rtol=1e-4, atol=1e-5), na
+
+
+def test_every_returned_site_list_carries_its_live_count():
+    """What capacity mode returns is capacity-sized; the live row count has to arrive with every generated level's `locs`
+    (scn.sites), or a consumer takes the padding rows for sites.  Teacher-forced masks, so that both paths keep exactly
+    the same sites: trim() of each returned `locs` equals the classic path's, and so does trim() of the detached copies
+    GraphStep keeps (a dropped count would make trim() return the capacity-sized tensor)."""
+    from sgnn_amd import loss as L
+    from sgnn_amd.scn import metadata as MD
+    from sgnn_amd.scn.capacity import Capacity, trim
+    from sgnn_amd.scn.sites import attach, info
+    from sgnn_amd.train import GraphStep
+    lw = np.ones(5, dtype=np.float32)
+    batch = _batch(3)
+    locs, feats = batch['input']
+    n, B = int(locs.shape[0]), int(batch['sdf'].shape[0])
+    (_, toccs, _), _ = L.compute_targets_and_weights(batch['sdf'], batch['hierarchy'], 4, 3.0, True, batch['known'], 5.0, locs)
+    MD.COUNT_LOG = []
+    try:
+        sa, oa = _model()(batch['input'], lw, batch_size=B, teacher=toccs)
+        log = MD.COUNT_LOG
+    finally:
+        MD.COUNT_LOG = None
+    cap = Capacity.from_log('cuda', log, headroom=1.4)
+    slocs = torch.zeros(cap.input_rows, 4, dtype=torch.int64, device='cuda')
+    sfeats = torch.zeros(cap.input_rows, feats.shape[1], device='cuda')
+    slocs[:n], sfeats[:n] = locs, feats
+    attach(slocs, cnt=cap.input_cnt())
+    cap.set_input_rows(n)
+    sb, ob = _model()([slocs, sfeats], lw, batch_size=B, teacher=toccs, capacity=cap)
+    db, dob = GraphStep._detached(sb, ob)
+    assert info(ob[0][0]).cnt is None and torch.equal(ob[0][0], oa[0][0])      # the dense coarse volume: exact
+    assert info(dob[0][0]).cnt is None and torch.equal(dob[0][0], oa[0][0])
+    want = [o[0] for o in oa[1:]] + [sa[0]]
+    for name, levels in (('returned', ob[1:] + [sb]), ('detached', dob[1:] + [db])):
+        assert len(levels) == len(want) == 4
+        for h, ((gl, gv), w) in enumerate(zip(levels, want)):
+            assert info(gl).cnt is not None, (name, h)
+            assert gl.shape[0] > w.shape[0] > 0 and gv.shape[0] == gl.shape[0], (name, h)     # capacity-sized, as returned
+            assert torch.equal(trim(gl), w), (name, h)
 
 
 def test_flat_adam_is_adam():

@@ -84,6 +84,7 @@ def test_teacher_forced_compaction_equals_boolean_indexing():
     > 0.5 at its coordinates — stable order, sites outside the volume dropped — against torch boolean indexing; the
     plan variant (compaction + coordinates + stride-2 pyramid, one read-back) must agree with it."""
     from sgnn_amd.scn import functions as F_
+    from sgnn_amd.scn.sites import info
     g = torch.Generator().manual_seed(5)
     B, d = 3, 16
     vol = (torch.rand(B, 1, d, d, d, generator=g) < 0.3).float()
@@ -104,8 +105,8 @@ def test_teacher_forced_compaction_equals_boolean_indexing():
         assert cnt == int(want.numel()) and 0 < cnt < n
         assert torch.equal(sel.cpu(), want)
         assert torch.equal(locs.cpu(), coords[keep].to(torch.int32))
-        assert (getattr(locs, '_sgnn_plan', None) is not None) == (depth == 2)
-    grid0, downs = locs._sgnn_plan
+        assert (info(locs).plan is not None) == (depth == 2)
+    grid0, downs = info(locs).plan
     assert grid0.n == cnt and len(downs) == 2
     coarse = torch.unique(torch.cat([coords[keep][:, :3] // 2, coords[keep][:, 3:]], 1), dim=0)
     assert downs[0].coarse.n == coarse.shape[0]

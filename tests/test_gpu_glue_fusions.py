@@ -70,6 +70,7 @@ def test_compaction_with_locs_equals_compaction_plus_gather(keep_cap):
 
 def test_expand8_with_int64_rows_equals_the_two_launches():
     from sgnn_amd.scn import functions as F_
+    from sgnn_amd.scn.sites import info
     dev = torch.device('cuda')
     c = torch.randint(0, 500, (1234, 4), generator=torch.Generator().manual_seed(1), dtype=torch.int32).to(dev)
     was = F_.FUSED_GLUE
@@ -77,10 +78,10 @@ def test_expand8_with_int64_rows_equals_the_two_launches():
         F_.FUSED_GLUE = True
         a = F_.expand8_coords(c, with_i64=True)
         a64 = F_.coords_to_i64(a)
-        assert a64 is a._sgnn_i64
+        assert a64 is info(a).i64
         F_.FUSED_GLUE = False
         b = F_.expand8_coords(c, with_i64=True)
-        assert getattr(b, '_sgnn_i64', None) is None
+        assert info(b).i64 is None
         b64 = F_.coords_to_i64(b)
     finally:
         F_.FUSED_GLUE = was

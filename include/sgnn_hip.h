@@ -799,6 +799,31 @@ int sgnn_mesh_sample(const float *records, const double *cum, int ntri, int last
                      float *pts, int32_t *fid, sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * TSDF volumes ray-cast to depth and normal frames (sgnn_amd.raycast; rules in INTEGRATION.md section H): the way
+ * back from a volume to images, at the camera conventions of the fusion and render blocks above.  The volume is a
+ * dense (dz, dy, dx) f32 array in any unit, band in the same unit: a voxel is usable iff |sdf| < band (never for a
+ * NaN or an infinity).  The output is what sgnn_fuse_bilateral / sgnn_fuse_integrate take: one (nframes, h, w) f32
+ * stack of z-depths, -inf = no hit.
+ * ------------------------------------------------------------------------- */
+/* one frame of the cast below (64 bytes; the frame table is a device array of these) */
+typedef struct sgnn_raycast_frame {
+  float g[12];   /* rows 0..2 of world2grid . cam2world: camera (x,y,z,1) -> voxel coordinates, fp32; NaN = empty frame */
+  float intr[4]; /* fx, fy, cx, cy */
+} sgnn_raycast_frame;
+/* bricks[(bz * nby + by) * nbx + bx] = 1 iff the 8x8x8 brick holds a usable voxel, else 0; nb? = ceil(d? / 8),
+ * d? <= 65535 */
+int sgnn_raycast_bricks(const float *sdf, int dx, int dy, int dz, float band, uint8_t *bricks, sgnn_stream_t stream);
+/* depth (nframes, h, w) f32 and, with normal != NULL, normal (nframes, h, w, 3) f32 in camera space (NaN = none).
+ * Samples sit at depth_min + (float)k * dt for k < nsamples (<= 2^20).  bricks: the table of the pass above for the
+ * same volume and band, or NULL to visit every sample; chunk: frames per launch (<= 0: all); the result depends on
+ * neither.  counters: NULL, or device int64[2] that the call adds to (measurements and tests): samples put through
+ * the range test and the eight corner fetches, samples passed over through the brick table.
+ * nframes * h * w < 2^31. */
+int sgnn_raycast_cast(const float *sdf, int dx, int dy, int dz, float band, const uint8_t *bricks,
+                      const sgnn_raycast_frame *frames, int nframes, int chunk, int h, int w, float depth_min, float dt,
+                      int nsamples, float *depth, float *normal, int64_t *counters, sgnn_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Evaluation metrics on the device.
  * ------------------------------------------------------------------------- */
 /* IoU ingredients of one hierarchy level (torch/loss.py:84-120 compute_iou_sparse_dense, fed as in

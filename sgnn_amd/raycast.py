@@ -1,0 +1,135 @@
+"""TSDF volumes ray-cast to depth and normal frames on the GPU: the way back from a volume to images.
+
+sgnn_amd.render turns a mesh into depth frames and sgnn_amd.fusion turns depth frames into a volume; this module
+closes the loop without a mesh in between: a scan volume, a target volume or a prediction seen from any camera pose,
+compared in depth space with the frames it was fused from (or with render.render_depth of a ground-truth mesh), or
+scanned again for fusion.  The reference project has no counterpart; the rules this follows are listed in
+INTEGRATION.md section H, and that text is the contract of the kernels (sgnn_amd/csrc/raycast.hip) and of the
+independent NumPy restatement of the tests (tests/raycast_ref.py).
+
+    vol = fusion.TSDFVolume(dims, 0.02, world2grid).integrate(depth, K, poses)
+    again = cast_volume(vol, K, poses, (240, 320))                      # (F, h, w) fp32 on the device, -inf = no hit
+    depth, normal = cast(sdf, world2grid, vs, K, poses, (240, 320), band, normals=True)
+    depth = cast_sparse(locs_zyx, vals, dims_zyx, world2grid, vs, K, poses, (240, 320), band)
+
+The host does per-frame geometry only (one 3x4 matrix per frame).
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from .fusion import _device, _host, _to_device
+
+# struct sgnn_raycast_frame (include/sgnn_hip.h)
+FRAME_DTYPE = np.dtype([('g', '<f4', (12,)), ('intr', '<f4', (4,))])
+assert FRAME_DTYPE.itemsize == 64
+
+DEFAULT_CHUNK = 0           # frames per launch, 0 = all in one
+MAX_SAMPLES = 1 << 20       # per ray
+
+
+def frame_table(intrinsics, cam2world, world2grid):
+    """Host table of sgnn_raycast_frame records (rule 1): rows 0..2 of world2grid . cam2world, formed in fp64 and
+    rounded to fp32, and fx, fy, cx, cy.  A pose that is not finite (or whose product is not finite in fp32) gets NaN
+    rows: its frame stays empty."""
+    k = _host(intrinsics, np.float32).reshape(-1, 4)
+    c2w = _host(cam2world, np.float64).reshape(-1, 4, 4)
+    w2g = _host(world2grid, np.float64).reshape(4, 4)
+    if c2w.shape[0] != k.shape[0]:
+        raise ValueError('%d intrinsics for %d poses' % (k.shape[0], c2w.shape[0]))
+    t = np.zeros(k.shape[0], dtype=FRAME_DTYPE)
+    with np.errstate(all='ignore'):
+        g = (w2g @ c2w)[:, :3, :].astype(np.float32)
+    g[~np.isfinite(g).all(axis=(1, 2)) | ~np.isfinite(c2w).all(axis=(1, 2))] = np.nan
+    t['g'] = g.reshape(-1, 12)
+    t['intr'] = k
+    return t
+
+
+def sample_count(depth_min, depth_max, dt):
+    """Samples per ray (rule 3): the number of k = 0, 1, .. with depth_min + (float)k * dt <= depth_max, all fp32."""
+    f32 = np.float32
+    dmin, dmax, dt = f32(depth_min), f32(depth_max), f32(dt)
+    est = (float(dmax) - float(dmin)) / float(dt)
+    if not est < 4 * MAX_SAMPLES:
+        return 4 * MAX_SAMPLES
+    at = lambda k: dmin + f32(k) * dt  # noqa: E731
+    k = int(est)
+    while k < MAX_SAMPLES and at(k + 1) <= dmax:
+        k += 1
+    while k > 0 and at(k) > dmax:
+        k -= 1
+    return k + 1
+
+
+def cast(sdf, world2grid, voxel_size, intrinsics, cam2world, hw, band, step=0.5, depth_min=0.4, depth_max=4.0,
+         normals=False, skip=True, chunk=None, counters=None):
+    """z-depth of the zero crossing of a signed-distance volume seen from F cameras -> (F, h, w) fp32 on the device,
+    -inf where a ray meets no front-facing crossing; with normals=True also (F, h, w, 3) fp32 unit normals in camera
+    space, facing the camera, NaN where there is no hit or no gradient.
+
+    sdf (Z, Y, X) fp32 in any unit, positive in front of surfaces (TSDFVolume.sdf(), marching_cubes.dense_from_sparse),
+    band in the same unit: voxels with |sdf| >= band, NaN or an infinity are unknown.  world2grid (4, 4): world metres
+    -> voxel coordinates; voxel_size in metres; step: sample spacing in voxels (z-depth); intrinsics (F, 4) fx, fy,
+    cx, cy; cam2world (F, 4, 4); numpy arrays or torch tensors, host or device.  skip: pass over empty space through a
+    brick table; chunk: frames per launch (None: DEFAULT_CHUNK); the result depends on neither.  counters: None, or a
+    device int64 tensor of 2 that receives samples evaluated and samples skipped (measurements)."""
+    dev = _device(sdf.device if torch.is_tensor(sdf) and sdf.is_cuda else None)
+    if len(tuple(sdf.shape)) != 3:
+        raise ValueError('sdf must be (Z, Y, X), got %s' % (tuple(sdf.shape),))
+    dz, dy, dx = (int(v) for v in sdf.shape)
+    if min(dx, dy, dz) < 1 or max(dx, dy, dz) > 65535:
+        raise ValueError('unsupported volume dimensions %s' % ((dz, dy, dx),))
+    h, w = (int(v) for v in hw)
+    if h < 1 or w < 1:
+        raise ValueError('unsupported frame size %s' % ((h, w),))
+    f32 = np.float32
+    band, step, vs = f32(band), f32(step), f32(voxel_size)
+    dmin, dmax = f32(depth_min), f32(depth_max)
+    for name, v in (('band', band), ('step', step), ('voxel_size', vs)):
+        if not v > 0:
+            raise ValueError('%s must be positive' % name)
+    if not (np.isfinite(dmin) and np.isfinite(dmax)) or dmax < dmin:
+        raise ValueError('depth_min = %s, depth_max = %s is not a range' % (depth_min, depth_max))
+    if np.ndim(intrinsics) != 2 or tuple(np.shape(intrinsics))[1:] != (4,):
+        raise ValueError('intrinsics must be (F, 4), got %s' % (tuple(np.shape(intrinsics)),))
+    if np.ndim(cam2world) != 3 or tuple(np.shape(cam2world))[1:] != (4, 4):
+        raise ValueError('cam2world must be (F, 4, 4), got %s' % (tuple(np.shape(cam2world)),))
+    table = frame_table(intrinsics, cam2world, world2grid)
+    nf = int(table.shape[0])
+    if nf * h * w >= 2 ** 31:
+        raise ValueError('F h w = %d does not fit 31 bits' % (nf * h * w))
+    dt = step * vs                                                       # one fp32 product (rule 3)
+    if not (dt > 0 and np.isfinite(dt)):
+        raise ValueError('step * voxel_size = %s is not a usable sample spacing' % dt)
+    ns = sample_count(dmin, dmax, dt)
+    if ns > MAX_SAMPLES:
+        raise ValueError('more than %d samples per ray' % MAX_SAMPLES)
+    vol = _to_device(sdf, torch.float32, dev)
+    depth = torch.empty((nf, h, w), dtype=torch.float32, device=dev)
+    normal = torch.empty((nf, h, w, 3), dtype=torch.float32, device=dev) if normals else None
+    if nf:
+        bricks = None
+        if skip:
+            bricks = torch.empty(((dz + 7) // 8, (dy + 7) // 8, (dx + 7) // 8), dtype=torch.uint8, device=dev)
+            _lib.call('sgnn_raycast_bricks', vol.data_ptr(), dx, dy, dz, float(band), bricks.data_ptr())
+        dev_table = torch.from_numpy(table.view(np.uint8)).to(dev)
+        _lib.call('sgnn_raycast_cast', vol.data_ptr(), dx, dy, dz, float(band), _lib.ptr(bricks), dev_table.data_ptr(),
+                  nf, int(DEFAULT_CHUNK if chunk is None else chunk), h, w, float(dmin), float(dt), ns,
+                  depth.data_ptr(), _lib.ptr(normal), _lib.ptr(counters))
+    return (depth, normal) if normals else depth
+
+
+def cast_volume(vol, intrinsics, cam2world, hw, band=None, **kwargs):
+    """cast() of a fusion.TSDFVolume: its sdf in metres, its world2grid and voxel size; band: 3 voxel sizes (one fp32
+    product) unless given.  depth_min / depth_max default to cast()'s, not to the volume's."""
+    band = np.float32(3.0) * vol.voxel_size if band is None else band
+    return cast(vol.sdf(), vol.world2grid, vol.voxel_size, intrinsics, cam2world, hw, band, **kwargs)
+
+
+def cast_sparse(locs_zyx, vals, dims_zyx, world2grid, voxel_size, intrinsics, cam2world, hw, band, **kwargs):
+    """cast() of sparse rows (locs (N, 3) z, y, x and vals (N,)), through marching_cubes.dense_from_sparse: voxels
+    without a row are unknown."""
+    from .marching_cubes import dense_from_sparse
+    return cast(dense_from_sparse(locs_zyx, vals, dims_zyx), world2grid, voxel_size, intrinsics, cam2world, hw, band,
+                **kwargs)

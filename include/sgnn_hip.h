@@ -342,7 +342,9 @@ int sgnn_bn_bwd_ex(const float *x, int64_t ldx, const float *dy, int64_t ld_dy, 
                    const double *pre_partial, int64_t pre_nblk, void *ws, int64_t ws_bytes, sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
- * Row movement (all pure copies / sums, fp32 rows of c floats)
+ * Row movement (all pure copies / sums, fp32 rows of c floats).  Rows move as float4 when c % 4 == 0 and every base
+ * pointer is 16-byte aligned, float by float otherwise (a contiguous view at an odd float offset of a larger buffer);
+ * same values either way.
  * ------------------------------------------------------------------------- */
 /* Up to 8 device-to-device copies as one launch: dst[k] <- src[k], bytes[k] bytes each (host arrays of device pointers /
  * sizes; regions must not overlap each other).  train.GraphStep loads a batch into the replayed graph's static input

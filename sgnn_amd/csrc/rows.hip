@@ -8,8 +8,14 @@
 #include <initializer_list>
 #include "common.h"
 
-// vector width (floats) usable for rows of c floats
-static inline int row_vec(int c) { return (c % 4 == 0) ? 4 : 1; }
+// vector width (floats) usable for contiguous rows of c floats at these base pointers: float4 needs c % 4 == 0 and every
+// base 16-byte aligned (a contiguous view that starts at an odd float offset of a larger buffer takes the scalar form)
+static inline int row_vec(int c, std::initializer_list<const void *> ptrs) {
+  if (c % 4) return 1;
+  for (const void *p : ptrs)
+    if ((uintptr_t)p & 15) return 1;
+  return 4;
+}
 
 template <int VEC>
 struct VecT;
@@ -28,10 +34,10 @@ __device__ __forceinline__ float vzero<1>() { return 0.f; }
 __device__ __forceinline__ float4 vadd(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float vadd(float a, float b) { return a + b; }
 
-#define ROWS_LAUNCH(KERNEL, c, total_groups, stream, ...)                                              \
+#define ROWS_LAUNCH(KERNEL, vec, total_groups, stream, ...)                                              \
   do {                                                                                                 \
     const int grid_ = sgnn_grid_for((total_groups), 256, 4096);                                        \
-    if (row_vec(c) == 4)                                                                               \
+    if ((vec) == 4)                                                                                    \
       SGNN_LAUNCH((KERNEL<4>), dim3(grid_), dim3(256), 0, (hipStream_t)(stream), __VA_ARGS__);  \
     else                                                                                               \
       SGNN_LAUNCH((KERNEL<1>), dim3(grid_), dim3(256), 0, (hipStream_t)(stream), __VA_ARGS__);  \
@@ -170,8 +176,8 @@ SGNN_EXPORT int sgnn_gather_rows(const float *src, int c, const int32_t *idx, in
   SGNN_CHECK_ARG(c >= 1 && m >= 0);
   if (m == 0) return SGNN_OK;
   SGNN_CHECK_ARG(src && idx && dst);
-  const int cq = c / row_vec(c);
-  ROWS_LAUNCH(k_gather_rows, c, m * cq, stream, src, cq, idx, m, dst);
+  const int vec = row_vec(c, {src, dst}), cq = c / vec;
+  ROWS_LAUNCH(k_gather_rows, vec, m * cq, stream, src, cq, idx, m, dst);
   SGNN_CHECK_LAUNCH();
   return SGNN_OK;
 }
@@ -304,8 +310,8 @@ SGNN_EXPORT int sgnn_gather_rows_dn(const float *src, int c, const int32_t *idx,
   SGNN_CHECK_ARG(c >= 1 && m_cap >= 0 && m_dev);
   if (m_cap == 0) return SGNN_OK;
   SGNN_CHECK_ARG(src && idx && dst);
-  const int cq = c / row_vec(c);
-  ROWS_LAUNCH(k_gather_rows_dn, c, m_cap * cq, stream, src, cq, idx, m_dev, m_cap, dst);
+  const int vec = row_vec(c, {src, dst}), cq = c / vec;
+  ROWS_LAUNCH(k_gather_rows_dn, vec, m_cap * cq, stream, src, cq, idx, m_dev, m_cap, dst);
   SGNN_CHECK_LAUNCH();
   return SGNN_OK;
 }
@@ -335,8 +341,8 @@ SGNN_EXPORT int sgnn_scatter_rows(const float *src, int c, const int32_t *idx, i
   }
   if (m == 0 || n_dst == 0) return SGNN_OK;
   SGNN_CHECK_ARG(src && idx);
-  const int cq = c / row_vec(c);
-  ROWS_LAUNCH(k_scatter_rows, c, m * cq, stream, src, cq, idx, m, dst, m_dev);
+  const int vec = row_vec(c, {src, dst}), cq = c / vec;
+  ROWS_LAUNCH(k_scatter_rows, vec, m * cq, stream, src, cq, idx, m, dst, m_dev);
   SGNN_CHECK_LAUNCH();
   return SGNN_OK;
 }
@@ -365,8 +371,8 @@ SGNN_EXPORT int sgnn_gather_sum(const float *src, int c, const int32_t *table, i
   SGNN_CHECK_ARG(c >= 1 && n_out >= 0 && K >= 1 && ld >= n_out);
   if (n_out == 0) return SGNN_OK;
   SGNN_CHECK_ARG(src && table && dst);
-  const int cq = c / row_vec(c);
-  ROWS_LAUNCH(k_gather_sum, c, n_out * cq, stream, src, cq, table, ld, K, n_out, dst);
+  const int vec = row_vec(c, {src, dst}), cq = c / vec;
+  ROWS_LAUNCH(k_gather_sum, vec, n_out * cq, stream, src, cq, table, ld, K, n_out, dst);
   SGNN_CHECK_LAUNCH();
   return SGNN_OK;
 }
@@ -387,8 +393,8 @@ SGNN_EXPORT int sgnn_repeat_rows(const float *src, int c, int64_t n, int rep, fl
   SGNN_CHECK_ARG(c >= 1 && n >= 0 && rep >= 1);
   if (n == 0) return SGNN_OK;
   SGNN_CHECK_ARG(src && dst);
-  const int cq = c / row_vec(c);
-  ROWS_LAUNCH(k_repeat_rows, c, n * rep * cq, stream, src, cq, n, rep, dst);
+  const int vec = row_vec(c, {src, dst}), cq = c / vec;
+  ROWS_LAUNCH(k_repeat_rows, vec, n * rep * cq, stream, src, cq, n, rep, dst);
   SGNN_CHECK_LAUNCH();
   return SGNN_OK;
 }
@@ -421,8 +427,8 @@ int sgnn_sum_groups_dn(const float *src, int c, int64_t n, int rep, float *dst, 
   SGNN_CHECK_ARG(c >= 1 && n >= 0 && rep >= 1);
   if (n == 0) return SGNN_OK;
   SGNN_CHECK_ARG(src && dst);
-  const int cq = c / row_vec(c);
-  ROWS_LAUNCH(k_sum_groups, c, n * cq, stream, src, cq, n, rep, dst, n_dev);
+  const int vec = row_vec(c, {src, dst}), cq = c / vec;
+  ROWS_LAUNCH(k_sum_groups, vec, n * cq, stream, src, cq, n, rep, dst, n_dev);
   SGNN_CHECK_LAUNCH();
   return SGNN_OK;
 }
@@ -677,9 +683,15 @@ int sgnn_concat3_rows_bwd_dn(const float *ddst, int ca, const int32_t *ia, int c
   return SGNN_OK;
 }
 
+// vec: float4 body + scalar tail (all three bases 16-byte aligned); otherwise one float per thread
 __global__ __launch_bounds__(256) void k_add(const float *__restrict__ a, const float *__restrict__ b,
-                                            int64_t count, float *__restrict__ y) {
-  const int64_t n4 = count / 4, stride = (int64_t)gridDim.x * 256;
+                                            int64_t count, float *__restrict__ y, int vec) {
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  if (!vec) {
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < count; g += stride) y[g] = a[g] + b[g];
+    return;
+  }
+  const int64_t n4 = count / 4;
   for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n4; g += stride) {
     const float4 u = reinterpret_cast<const float4 *>(a)[g], v = reinterpret_cast<const float4 *>(b)[g];
     reinterpret_cast<float4 *>(y)[g] = make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w);
@@ -694,8 +706,9 @@ SGNN_EXPORT int sgnn_add(const float *a, const float *b, int64_t count, float *y
   SGNN_CHECK_ARG(count >= 0);
   if (count == 0) return SGNN_OK;
   SGNN_CHECK_ARG(a && b && y);
-  SGNN_LAUNCH(k_add, dim3(sgnn_grid_for(count / 4 + 1, 256, 4096)), dim3(256), 0, (hipStream_t)stream, a, b,
-                     count, y);
+  const int vec = ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)y)) & 15) == 0;
+  SGNN_LAUNCH(k_add, dim3(sgnn_grid_for(vec ? count / 4 + 1 : count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, a, b,
+                     count, y, vec);
   SGNN_CHECK_LAUNCH();
   return SGNN_OK;
 }

@@ -826,6 +826,42 @@ int sgnn_raycast_cast(const float *sdf, int dx, int dy, int dz, float band, cons
                       int nsamples, float *depth, float *normal, int64_t *counters, sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Depth frames tracked against a volume (sgnn_amd.track; rules in INTEGRATION.md section I): the "frame to model"
+ * half that goes with the cast above.  One Gauss-Newton system of projective point-to-plane ICP per (live frame,
+ * model frame) pair, the depth pyramid and the live normals; the 6x6 solve and the pose update stay on the host.
+ * Frames are (n, h, w) f32 z-depths, -inf = no depth, at the camera conventions of the blocks above; the model
+ * depth and normal frames are what sgnn_raycast_cast writes.
+ * ------------------------------------------------------------------------- */
+/* one (live frame, model frame) pair of sgnn_track_system (96 bytes; the pair table is a device array of these) */
+typedef struct sgnn_track_pair {
+  float t[12];         /* rows 0..2 of T = inv(model cam2world) . live cam2world: live camera (x,y,z,1) -> model
+                          camera, fp32; NaN = non-finite pose, empty system */
+  float intr_live[4];  /* fx, fy, cx, cy of the live frame */
+  float intr_model[4]; /* fx, fy, cx, cy of the model frame */
+  float pad[4];
+} sgnn_track_pair;
+#define SGNN_TRACK_MAX_BLOCKS 256 /* partial sums per pair that sgnn_track_system keeps in its workspace */
+/* out (nframes, h/2, w/2) f32: per 2x2 block the mean of the finite values within delta of the smallest finite one
+ * (rule 9), -inf if none.  nframes * h * w < 2^31; an empty output (h or w of 1, no frame) launches nothing. */
+int sgnn_track_halve(const float *depth, int nframes, int h, int w, float delta, float *out, sgnn_stream_t stream);
+/* normal (nframes, h, w, 3) f32: camera-space unit normals of a depth frame from its four axis neighbours (rule 10),
+ * facing the camera, NaN = none.  intr (nframes, 4) f32 on the device: fx, fy, cx, cy.  nframes * h * w < 2^31. */
+int sgnn_track_normals(const float *depth, const float *intr, int nframes, int h, int w, float delta, float *normal,
+                       sgnn_stream_t stream);
+/* out (npairs, 32) f64: per pair the 21 sums of the upper triangle of J^T J (row-major), the 6 of J^T r, the sum of
+ * r^2, the number of associated pixels, and three zeros (rules 2-6).  depth (npairs, h, w); live_normal (npairs, h,
+ * w, 3) or NULL (no angle gate); model_depth (npairs, hm, wm) and model_normal (npairs, hm, wm, 3).  max_dist2: the
+ * squared distance gate, cos_min: the angle gate, both rounded by the caller.  residual (npairs, h, w) f32 (NaN = no
+ * association) and assoc (npairs, h, w) i32 (v * wm + u, or -1) may be NULL.  ws: at least npairs *
+ * min(ceil(h * w / 256), SGNN_TRACK_MAX_BLOCKS) * 256 bytes; the number of partial sums depends on (h, w) alone and
+ * they are added in index order, so neither npairs nor the launch shows in any bit of the result.
+ * npairs <= 65535; npairs * h * w and npairs * hm * wm < 2^31. */
+int sgnn_track_system(const float *depth, const float *live_normal, int h, int w, const float *model_depth,
+                      const float *model_normal, int hm, int wm, const sgnn_track_pair *pairs, int npairs,
+                      float max_dist2, float cos_min, double *out, float *residual, int32_t *assoc, void *ws,
+                      int64_t ws_bytes, sgnn_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Evaluation metrics on the device.
  * ------------------------------------------------------------------------- */
 /* IoU ingredients of one hierarchy level (torch/loss.py:84-120 compute_iou_sparse_dense, fed as in

@@ -8,6 +8,7 @@ Package contents (only what the hot path of SURVEY.md §8 needs):
   loss.py      compute_targets / compute_loss (torch/loss.py:15-199)
   train.py     one training step + data-parallel gradient all-reduce (torch/train.py:245-268)
   synth.py     synthetic TSDF blocks in the layout scene_dataloader.collate emits
+  track.py     depth frames tracked against a TSDF volume: poses for fusion
 """
 __version__ = '0.1.0'
 
@@ -18,4 +19,7 @@ def __getattr__(name):
     if name == 'bf16_inference':
         from .scn.program import bf16_inference
         return bf16_inference
+    if name == 'track':             # sgnn_amd.track without an import statement of its own, as lazily as the above
+        import importlib
+        return importlib.import_module('.track', __name__)
     raise AttributeError(name)

@@ -152,6 +152,10 @@ PROTOTYPES = {
     'sgnn_raycast_bricks': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp]),
     'sgnn_raycast_cast': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32,
                                   c_i32, c_vp, c_vp, c_vp, c_vp]),
+    'sgnn_track_halve': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp]),
+    'sgnn_track_normals': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp]),
+    'sgnn_track_system': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_f32, c_f32, c_vp, c_vp,
+                                  c_vp, c_vp, c_i64, c_vp]),
     'sgnn_iou_counts': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'sgnn_l1_tgtsurf_ws_bytes': (c_i64, []),
     'sgnn_l1_tgtsurf': (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp, c_i64, c_vp]),

@@ -1,0 +1,338 @@
+"""Depth frames tracked against a TSDF volume on the GPU: camera poses for sequences that arrive without any.
+
+sgnn_amd.raycast is the "model to frame" half of a KinectFusion-style system; this module is the other half, frame to
+model: projective point-to-plane ICP of a live depth frame against the depth and normal maps that
+raycast.cast_volume(..., normals=True) returns, giving the cam2world that fusion.TSDFVolume.integrate takes.  The
+reference project has no counterpart; the rules this follows are listed in INTEGRATION.md section I, and that text is
+the contract of the kernels (sgnn_amd/csrc/track.hip) and of the independent NumPy restatement of the tests
+(tests/track_ref.py).
+
+    vol = fusion.TSDFVolume(dims, 0.02, world2grid)
+    poses, results = track_sequence(vol, depth_frames, K, first_pose)      # tracks and fuses, frame by frame
+    res = align(depth, K, model_pose, guess_pose, vol)                      # one frame: TrackResult
+    sys = normal_equations(depth, K, model_depth, model_normal, K_model, T)  # (B, 32) fp64 on the device
+
+The device builds the Gauss-Newton systems, the depth pyramid and the live normals; the 6x6 solve and the pose update
+run on the host in fp64 (one 256-byte read-back per iteration), in the same spirit as raycast.frame_table.
+"""
+import collections
+import math
+
+import numpy as np
+import torch
+
+from . import _lib, raycast
+from .fusion import _device, _host, _to_device
+
+# struct sgnn_track_pair (include/sgnn_hip.h)
+PAIR_DTYPE = np.dtype([('t', '<f4', (12,)), ('intr_live', '<f4', (4,)), ('intr_model', '<f4', (4,)),
+                       ('pad', '<f4', (4,))])
+assert PAIR_DTYPE.itemsize == 96
+
+MAX_BLOCKS = 256            # SGNN_TRACK_MAX_BLOCKS
+MAX_PAIRS = 65535
+# entries of one system (rule 6)
+A_SLICE, G_SLICE, E_INDEX, N_INDEX = slice(0, 21), slice(21, 27), 27, 28
+_TRIU = np.triu_indices(6)
+
+TrackResult = collections.namedtuple('TrackResult', 'pose ok pairs rmse iterations history')
+TrackResult.__doc__ = """What align() found for one frame: pose (4, 4) fp64 cam2world (the guess when ok is false), ok,
+pairs and rmse (metres) of the finest level's last iteration, iterations run, and history: the number of associated
+pixels of every iteration in the order they ran (coarse to fine)."""
+
+
+def _frames(x, name, tail=()):
+    """Shape of a (B, h, w) + tail stack, checked."""
+    shape = tuple(int(v) for v in x.shape)
+    if len(shape) != 3 + len(tail) or shape[3:] != tuple(tail):
+        raise ValueError('%s must be (B, h, w%s), got %s' % (name, ''.join(', %d' % t for t in tail), shape))
+    if shape[1] < 1 or shape[2] < 1:
+        raise ValueError('unsupported frame size %s' % (shape[1:3],))
+    if shape[0] * shape[1] * shape[2] >= 2 ** 31:
+        raise ValueError('B h w = %d does not fit 31 bits' % (shape[0] * shape[1] * shape[2]))
+    return shape
+
+
+def _intrinsics(k, nb, name):
+    """(nb, 4) fp32 host intrinsics from (4,) or (nb, 4)."""
+    k = _host(k, np.float32)
+    if k.shape == (4,):
+        k = np.tile(k, (nb, 1))
+    if k.ndim != 2 or k.shape[1] != 4:
+        raise ValueError('%s must be (B, 4) or (4,), got %s' % (name, k.shape))
+    if k.shape[0] != nb:
+        raise ValueError('%d %s for %d frames' % (k.shape[0], name, nb))
+    return np.ascontiguousarray(k)
+
+
+def _positive(**values):
+    for name, v in values.items():
+        if not (np.float32(v) > 0 and np.isfinite(np.float32(v))):
+            raise ValueError('%s must be positive' % name)
+
+
+def _source_device(x):
+    return _device(x.device if torch.is_tensor(x) and x.is_cuda else None)
+
+
+def pair_table(intrinsics, model_intrinsics, T):
+    """Host table of sgnn_track_pair records (rule 1): rows 0..2 of T rounded to fp32 and the two sets of fx, fy, cx,
+    cy.  A T that is not finite (in fp64 or after rounding) gets NaN rows: its system stays empty."""
+    t64 = _host(T, np.float64)
+    if t64.ndim != 3 or t64.shape[1:] != (4, 4):
+        raise ValueError('T must be (B, 4, 4), got %s' % (t64.shape,))
+    nb = t64.shape[0]
+    table = np.zeros(nb, dtype=PAIR_DTYPE)
+    with np.errstate(all='ignore'):
+        t = t64[:, :3, :].astype(np.float32)
+    t[~np.isfinite(t).all(axis=(1, 2)) | ~np.isfinite(t64).all(axis=(1, 2))] = np.nan
+    table['t'] = t.reshape(nb, 12)
+    table['intr_live'] = _intrinsics(intrinsics, nb, 'intrinsics')
+    table['intr_model'] = _intrinsics(model_intrinsics, nb, 'model intrinsics')
+    return table
+
+
+def normal_equations(depth, K, model_depth, model_normal, K_model, T, max_dist=0.1, max_angle_deg=20.0,
+                     live_normal=None, residual=None, assoc=None):
+    """One Gauss-Newton system of point-to-plane ICP per (live frame, model frame) pair -> (B, 32) fp64 on the device:
+    the 21 sums of the upper triangle of J^T J (row-major), the 6 of J^T r, the sum of r^2, the number of associated
+    pixels, three zeros (rules 2-6; unpack() gives A, g, E, N).
+
+    depth (B, h, w) live z-depths, -inf = none; K (B, 4) or (4,) fx, fy, cx, cy; model_depth (B, hm, wm) and
+    model_normal (B, hm, wm, 3) as raycast.cast(..., normals=True) returns them, K_model their intrinsics; T (B, 4, 4):
+    live camera -> model camera, inv(model_pose) . live_pose.  max_dist: the distance gate in metres; live_normal
+    (B, h, w, 3) switches the angle gate on (max_angle_deg between the rotated live normal and the model normal).
+    residual: None or a device fp32 tensor (B, h, w) that receives r, NaN where a pixel has no association; assoc:
+    None or a device int32 tensor (B, h, w) that receives v * wm + u, or -1.  numpy arrays or torch tensors, host or
+    device."""
+    dev = _source_device(depth)
+    nb, h, w = _frames(depth, 'depth')
+    mb, hm, wm = _frames(model_depth, 'model_depth')
+    _frames(model_normal, 'model_normal', (3,))
+    if mb != nb or tuple(int(v) for v in model_normal.shape[:3]) != (mb, hm, wm):
+        raise ValueError('%d live frames, model depth %s, model normals %s' % (nb, tuple(model_depth.shape),
+                                                                              tuple(model_normal.shape)))
+    if live_normal is not None and _frames(live_normal, 'live_normal', (3,))[:3] != (nb, h, w):
+        raise ValueError('live_normal %s for depth %s' % (tuple(live_normal.shape), (nb, h, w)))
+    if nb > MAX_PAIRS:
+        raise ValueError('more than %d pairs in one call' % MAX_PAIRS)
+    _positive(max_dist=max_dist, max_angle_deg=max_angle_deg)
+    max_dist2 = np.float32(max_dist) * np.float32(max_dist)             # one fp32 product (rule 4)
+    if not (max_dist2 > 0 and np.isfinite(max_dist2)):
+        raise ValueError('max_dist = %s is not a usable gate' % max_dist)
+    cos_min = np.float32(math.cos(math.radians(float(max_angle_deg))))
+    table = pair_table(K, K_model, T)
+    if table.shape[0] != nb:
+        raise ValueError('%d matrices for %d frames' % (table.shape[0], nb))
+    for name, t, dtype in (('residual', residual, torch.float32), ('assoc', assoc, torch.int32)):
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and
+                                  tuple(t.shape) == (nb, h, w)):
+            raise ValueError('%s must be a contiguous device %s tensor of shape %s' % (name, dtype, (nb, h, w)))
+    out = torch.zeros((nb, 32), dtype=torch.float64, device=dev)
+    if nb == 0:
+        return out
+    d = _to_device(depth, torch.float32, dev)
+    md = _to_device(model_depth, torch.float32, dev)
+    mn = _to_device(model_normal, torch.float32, dev)
+    ln = None if live_normal is None else _to_device(live_normal, torch.float32, dev)
+    nblk = min((h * w + 255) // 256, MAX_BLOCKS)
+    ws = torch.empty(nb * nblk * 32, dtype=torch.float64, device=dev)
+    dev_table = torch.from_numpy(table.view(np.uint8)).to(dev)
+    _lib.call('sgnn_track_system', d.data_ptr(), _lib.ptr(ln), h, w, md.data_ptr(), mn.data_ptr(), hm, wm,
+              dev_table.data_ptr(), nb, float(max_dist2), float(cos_min), out.data_ptr(), _lib.ptr(residual),
+              _lib.ptr(assoc), ws.data_ptr(), ws.numel() * 8)
+    return out
+
+
+def unpack(system):
+    """One 32-entry system (host) -> (A (6, 6) symmetric, g (6,), E, N)."""
+    s = np.asarray(system, np.float64).reshape(32)
+    a = np.zeros((6, 6))
+    a[_TRIU] = s[A_SLICE]
+    a = a + np.triu(a, 1).T
+    return a, s[G_SLICE].copy(), float(s[E_INDEX]), int(s[N_INDEX])
+
+
+def level_intrinsics(K):
+    """Intrinsics of the next pyramid level (rule 9): fx/2, fy/2, (cx - 0.5)/2, (cy - 0.5)/2, formed in fp64 and rounded
+    to fp32; (.., 4) -> (.., 4) fp32 numpy."""
+    k = _host(K, np.float32).astype(np.float64)
+    return np.stack([k[..., 0] / 2, k[..., 1] / 2, (k[..., 2] - 0.5) / 2, (k[..., 3] - 0.5) / 2], -1).astype(np.float32)
+
+
+def halve(depth, K, delta=0.05):
+    """The next pyramid level of (B, h, w) depth frames -> ((B, h // 2, w // 2) fp32 on the device, its intrinsics as
+    fp32 numpy).  A 2x2 block gives the mean of its finite values within delta of the smallest finite one, -inf if it
+    has none (rule 9): a depth edge is not blurred into a surface that is not there."""
+    dev = _source_device(depth)
+    nb, h, w = _frames(depth, 'depth')
+    _positive(delta=delta)
+    k = _host(K, np.float32)
+    if k.shape != (4,):
+        k = _intrinsics(k, nb, 'intrinsics')
+    d = _to_device(depth, torch.float32, dev)
+    out = torch.empty((nb, h // 2, w // 2), dtype=torch.float32, device=dev)
+    if out.numel():
+        _lib.call('sgnn_track_halve', d.data_ptr(), nb, h, w, float(np.float32(delta)), out.data_ptr())
+    return out, level_intrinsics(k)
+
+
+def depth_normals(depth, K, delta=0.05):
+    """Camera-space unit normals of (B, h, w) depth frames -> (B, h, w, 3) fp32 on the device, facing the camera (the
+    sign raycast gives), NaN where a pixel or one of its four axis neighbours is missing or more than delta away in
+    depth (rule 10)."""
+    dev = _source_device(depth)
+    nb, h, w = _frames(depth, 'depth')
+    _positive(delta=delta)
+    k = _intrinsics(K, nb, 'intrinsics')
+    d = _to_device(depth, torch.float32, dev)
+    out = torch.empty((nb, h, w, 3), dtype=torch.float32, device=dev)
+    if nb:
+        _lib.call('sgnn_track_normals', d.data_ptr(), torch.from_numpy(k).to(dev).data_ptr(), nb, h, w,
+                  float(np.float32(delta)), out.data_ptr())
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the host half (rule 8), fp64
+# ---------------------------------------------------------------------------------------------------------
+def _hat(w):
+    return np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+
+
+def se3_exp(xi):
+    """Closed-form exponential of the twist xi = (omega, t) -> (4, 4) fp64; the series below |omega| = 1e-8."""
+    xi = np.asarray(xi, np.float64).reshape(6)
+    w, t = xi[:3], xi[3:]
+    th = float(np.linalg.norm(w))
+    k = _hat(w)
+    k2 = k @ k
+    if th < 1e-8:
+        a, b, c = 1.0 - th * th / 6.0, 0.5 - th * th / 24.0, 1.0 / 6.0 - th * th / 120.0
+    else:
+        half = math.sin(0.5 * th)                                        # 1 - cos th = 2 sin^2(th / 2): no cancellation
+        a, b, c = math.sin(th) / th, 2.0 * half * half / (th * th), (th - math.sin(th)) / (th * th * th)
+    out = np.eye(4)
+    out[:3, :3] = np.eye(3) + a * k + b * k2
+    out[:3, 3] = (np.eye(3) + b * k + c * k2) @ t
+    return out
+
+
+def solve_step(system, min_pairs=64):
+    """One 32-entry system (host) -> (xi or None, N, E): A xi = -g by Cholesky; None when N < min_pairs or A is not
+    positive definite."""
+    a, g, e, n = unpack(system)
+    if n < min_pairs or not (np.isfinite(a).all() and np.isfinite(g).all()):
+        return None, n, e
+    try:
+        low = np.linalg.cholesky(a)
+    except np.linalg.LinAlgError:
+        return None, n, e
+    return np.linalg.solve(low.T, np.linalg.solve(low, -g)), n, e
+
+
+def align(depth, K, model_pose, guess_pose, volume, iterations=(10, 5, 4), max_dist=0.1, max_angle_deg=20.0,
+          min_pairs=64, delta=0.05, angle_gate=True, timers=None, **cast_kwargs):
+    """The pose of one depth frame against a fusion.TSDFVolume -> TrackResult.
+
+    depth (h, w) metres, -inf = none; K (4,) fx, fy, cx, cy; model_pose: the cam2world the volume is cast at (the
+    previous frame's pose); guess_pose: where the iteration starts.  iterations: Gauss-Newton steps per pyramid level,
+    finest first; the live frame is halved len(iterations) - 1 times, the volume is cast once per level at that
+    level's size and intrinsics (raycast.cast_volume(..., normals=True, **cast_kwargs)), and the levels run coarse to
+    fine with no early exit.  delta is the depth step of halve() and depth_normals() at the finest level; level l uses
+    delta * 2**l, since neighbouring pixels of one surface are twice as far apart.  angle_gate: compare
+    depth_normals() of the live level with the model normal.  ok is false when an iteration has fewer than min_pairs
+    associations or a system that is not positive definite; the pose returned is then the guess.  timers: None or a dict whose 'cast', 'system' and 'solve' entries get seconds added
+    (measurements; switches on a device synchronisation per stage)."""
+    dev = volume.device
+    if len(tuple(depth.shape)) != 2:
+        raise ValueError('depth must be (h, w), got %s' % (tuple(depth.shape),))
+    levels = len(iterations)
+    if levels < 1 or any(int(n) < 0 for n in iterations):
+        raise ValueError('iterations = %s' % (iterations,))
+    if int(depth.shape[0]) >> (levels - 1) < 1 or int(depth.shape[1]) >> (levels - 1) < 1:
+        raise ValueError('a %s frame has no %d levels' % (tuple(depth.shape), levels))
+    _positive(max_dist=max_dist, max_angle_deg=max_angle_deg, delta=delta)
+    model_pose = _host(model_pose, np.float64).reshape(4, 4)
+    guess_pose = _host(guess_pose, np.float64).reshape(4, 4)
+    tick = _Timer(timers)
+    d = [_to_device(depth, torch.float32, dev)[None]]
+    k = [_host(K, np.float32).reshape(4)]
+    deltas = [np.float32(delta) * np.float32(2 ** lv) for lv in range(levels)]     # the pixel pitch doubles per level
+    for lv in range(levels - 1):
+        half, kh = halve(d[-1], k[-1], deltas[lv])
+        d.append(half)
+        k.append(kh)
+    live_n = [depth_normals(dl, kl[None], dv) if angle_gate else None for dl, kl, dv in zip(d, k, deltas)]
+    tick('system')
+    model = [raycast.cast_volume(volume, kl[None], model_pose[None], tuple(dl.shape[1:]), normals=True, **cast_kwargs)
+             for dl, kl in zip(d, k)]
+    tick('cast')
+    with np.errstate(all='ignore'):
+        T = np.linalg.inv(model_pose) @ guess_pose if np.isfinite(model_pose).all() else np.full((4, 4), np.nan)
+    history, pairs, rmse = [], 0, float('nan')
+    for lv in range(levels - 1, -1, -1):
+        for _ in range(int(iterations[lv])):
+            system = normal_equations(d[lv], k[lv], model[lv][0], model[lv][1], k[lv], T[None], max_dist,
+                                      max_angle_deg, live_n[lv]).cpu().numpy()[0]      # 256 bytes
+            tick('system')
+            xi, pairs, e = solve_step(system, min_pairs)
+            history.append(pairs)
+            if xi is None:
+                tick('solve')
+                return TrackResult(guess_pose.copy(), False, pairs, float('nan'), len(history), tuple(history))
+            rmse = math.sqrt(e / pairs)
+            T = se3_exp(xi) @ T
+            tick('solve')
+    return TrackResult(model_pose @ T, True, pairs, rmse, len(history), tuple(history))
+
+
+class _Timer(object):
+    """Seconds per stage into a dict, or nothing at all."""
+
+    def __init__(self, sink):
+        self.sink = sink
+        if sink is not None:
+            import time
+            self.clock = time.perf_counter
+            torch.cuda.synchronize()
+            self.last = self.clock()
+
+    def __call__(self, stage):
+        if self.sink is None:
+            return
+        torch.cuda.synchronize()
+        now = self.clock()
+        self.sink[stage] = self.sink.get(stage, 0.0) + (now - self.last)
+        self.last = now
+
+
+def track_sequence(volume, depth_frames, K, first_pose, integrate=True, timers=None, **align_kwargs):
+    """Track a depth-only sequence against the volume it builds -> (poses (F, 4, 4) fp64 numpy, [TrackResult] * F).
+
+    With integrate, frame 0 is fused at first_pose; each later frame is aligned against a cast at the last tracked
+    frame's pose, with that pose as the guess, and fused when its result is ok.  A lost frame is skipped: it is
+    reported (ok false, pose = the guess) and not fused, and the next frame starts from the same pose again.
+    integrate=False tracks against the volume as it is and leaves it unchanged.  K (4,) or (F, 4); depth_frames
+    (F, h, w), host or device."""
+    nf, h, w = _frames(depth_frames, 'depth_frames')
+    k = _intrinsics(K, nf, 'intrinsics')
+    d = _to_device(depth_frames, torch.float32, volume.device)
+    pose = _host(first_pose, np.float64).reshape(4, 4).copy()
+    poses = np.tile(pose, (nf, 1, 1))
+    results = []
+    tick = _Timer(timers)
+    for f in range(nf):
+        if f == 0:
+            res = TrackResult(pose.copy(), True, 0, 0.0, 0, ())
+        else:
+            res = align(d[f], k[f], pose, pose, volume, timers=timers, **align_kwargs)
+            tick = _Timer(timers)
+        results.append(res)
+        poses[f] = res.pose
+        if res.ok:
+            pose = res.pose
+            if integrate:
+                volume.integrate(d[f:f + 1], k[f:f + 1], pose[None])
+                tick('integrate')
+    return poses, results

@@ -862,6 +862,40 @@ int sgnn_track_system(const float *depth, const float *live_normal, int h, int w
                       int64_t ws_bytes, sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Connected components of volumes and meshes (sgnn_amd.components; rules in INTEGRATION.md section J): lock-free
+ * union-find on parent[] (i32, one slot per voxel or vertex; -1 = background / unreferenced).  Larger indices are
+ * hooked onto smaller ones, so parent[i] <= i at all times and the root of a finished component is its smallest index.
+ *   sgnn_cc_volume_link -> parent of a (nb, dz, dy, dx) u8 mask (non-zero = foreground), connectivity 6, 18 or 26 inside
+ *                          one sample; nothing links across the batch axis or around a row end.  tiled != 0: every
+ *                          SGNN_CC_TILE_Z x _Y x _X tile is labelled in LDS first and only pairs that straddle a tile
+ *                          border are merged in global memory; tiled == 0: every pair is.  Both give the same
+ *                          components.
+ *   sgnn_cc_mesh_link   -> parent of nverts vertices: the three vertices of every face are joined.  A face with an
+ *                          index outside [0, nverts) is skipped before any access and raises
+ *                          SGNN_STATUS_COORD_RANGE in *status (status may be NULL).
+ *   sgnn_cc_flatten     -> parent[i] = root of i; is_root[i] = (parent[i] == i), u8
+ *   (caller: sel = sgnn_compact_mask(is_root), ncomp = its count; rank = sgnn_weld_number(sel): component k is the
+ *    one with the k-th smallest minimum index)
+ *   sgnn_cc_relabel     -> labels[i] = rank[parent[i]] or -1; sizes[k] (i64, zeroed by the caller) += members of k
+ *   sgnn_cc_face_labels -> face_labels[t] = vertex_labels[faces[t][0]] (-1 for a face with a bad index);
+ *                          face_sizes[k] (i64, zeroed by the caller) += faces of k
+ * Sizes are integer atomics: the same input gives the same output.  nb * dz * dy * dx < 2^31, nverts < 2^31,
+ * 3 * ntri < 2^31; a label outside [0, ncomp) is never used as an index.
+ * ------------------------------------------------------------------------- */
+#define SGNN_CC_TILE_Z 8
+#define SGNN_CC_TILE_Y 8
+#define SGNN_CC_TILE_X 32
+int sgnn_cc_volume_link(const uint8_t *mask, int nb, int dz, int dy, int dx, int connectivity, int tiled,
+                        int32_t *parent, sgnn_stream_t stream);
+int sgnn_cc_mesh_link(const int32_t *faces, int ntri, int nverts, int32_t *parent, int32_t *status,
+                      sgnn_stream_t stream);
+int sgnn_cc_flatten(int32_t *parent, int64_t n, uint8_t *is_root, sgnn_stream_t stream);
+int sgnn_cc_relabel(const int32_t *parent, int64_t n, const int32_t *rank, int64_t ncomp, int32_t *labels,
+                    int64_t *sizes, sgnn_stream_t stream);
+int sgnn_cc_face_labels(const int32_t *faces, int ntri, int nverts, const int32_t *vertex_labels, int64_t ncomp,
+                        int32_t *face_labels, int64_t *face_sizes, sgnn_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Evaluation metrics on the device.
  * ------------------------------------------------------------------------- */
 /* IoU ingredients of one hierarchy level (torch/loss.py:84-120 compute_iou_sparse_dense, fed as in

@@ -156,6 +156,11 @@ PROTOTYPES = {
     'sgnn_track_normals': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp]),
     'sgnn_track_system': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_f32, c_f32, c_vp, c_vp,
                                   c_vp, c_vp, c_i64, c_vp]),
+    'sgnn_cc_volume_link': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    'sgnn_cc_mesh_link': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    'sgnn_cc_flatten': (c_i32, [c_vp, c_i64, c_vp, c_vp]),
+    'sgnn_cc_relabel': (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    'sgnn_cc_face_labels': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
     'sgnn_iou_counts': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'sgnn_l1_tgtsurf_ws_bytes': (c_i64, []),
     'sgnn_l1_tgtsurf': (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp, c_i64, c_vp]),

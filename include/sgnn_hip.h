@@ -158,7 +158,9 @@ const sgnn_tune *sgnn_tune_current(void);
 
 /* 3x3x3 submanifold rulebook (scn.SubmanifoldConvolution, torch/model.py:32,38,40,179,186,254):
  * nbr[k*ld + j] = row of the site at p_j + d_k, k = (dz+1)*9+(dy+1)*3+(dx+1), else -1.
- * ld >= n; entries j in [n, ld) are written as -1. */
+ * ld >= n.  With m = the live row count (n, or *n_dev clamped to n), the entries j in [m, min(roundup256(m), ld)) are
+ * written as -1: the padding of the last 256-row tile that holds a live row, which is all the convolutions read.
+ * Entries at or beyond roundup256(m) are unspecified (some paths write -1 there, none has to). */
 int sgnn_rulebook_subm3(const uint64_t *keys, const int32_t *vals, int64_t cap,
                         const int32_t *coords, int64_t n, int32_t *nbr, int64_t ld,
                         const int64_t *n_dev, sgnn_stream_t stream);
@@ -206,7 +208,8 @@ int sgnn_rulebook_down2(const int32_t *fine_coords, int64_t nf, uint64_t *ckeys,
  *   children[k*ldc + c] = fine row whose parent is c and whose offset
  *                         (z&1)*4+(y&1)*2+(x&1) is k, else -1        (8 x ldc)
  *   ptable[k*ldf + i]   = parent[i] if offset(i)==k else -1          (8 x ldf)
- * (padding entries up to ldc / ldf are written as -1)
+ * (padding entries are written as -1 up to min(roundup256(live coarse rows), ldc) / min(roundup256(live fine rows), ldf);
+ *  entries beyond are unspecified, as for sgnn_rulebook_subm3)
  * children drives the forward conv / unpool-backward, ptable the data-gradient. */
 int sgnn_down2_tables(const int32_t *fine_coords, const int32_t *parent, int64_t nf,
                       int32_t *children, int64_t ldc, int64_t nc, int32_t *ptable, int64_t ldf,
@@ -249,7 +252,8 @@ int sgnn_down2_chain_tables(const int32_t *fine_coords, const int64_t *n0_dev, i
  * in_shift: feature row = table value >> in_shift (3 = features live on the
  * parents of an 8-child expansion, torch/model.py:192-207; 0 otherwise).
  * n_in = rows of x.  Table layout contract for the conv entry points: ld is a multiple of 256
- * and the padding entries table[k][n_out .. ld) are -1 (every table this library builds is so);
+ * and the padding entries table[k][m .. roundup256(m)) are -1, m = the live output rows (n_out, or the device count
+ * clamped to it): a table is read in tiles of at most 256 rows that start below m (every table this library builds is so);
  * K <= 64; each slab (x, y, table) must be smaller than 4 GiB (raw-buffer addressing).
  * ------------------------------------------------------------------------- */
 #define SGNN_CONV_TRANSPOSE_W 1

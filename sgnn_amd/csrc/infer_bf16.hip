@@ -373,7 +373,7 @@ int sgnn_bf16_conv_run(const void *x, int64_t n_in, int cin, int64_t ldx, const 
                  (!addend || ld_add >= cout));
   if (n_out == 0) return SGNN_OK;
   SGNN_CHECK_ARG(x && w && table && y && n_in >= 1);
-  SGNN_CHECK_ARG(ld % 256 == 0);   // and table[k][n_out..ld) must be -1 (as for sgnn_conv_fwd)
+  SGNN_CHECK_ARG(ld % 256 == 0);   // and table[k][n_out..roundup256(n_out)) must be -1 (as for sgnn_conv_fwd)
   if ((n_in * ldx + 64) * 2 > 0xFFFFF000ll || (int64_t)table_rows * ld * 4 > 0xFFFFF000ll) {
     sgnn_set_error("sgnn_bf16_conv: a slab exceeds the 4 GiB raw-buffer window (n_in=%lld, n_out=%lld)", (long long)n_in,
                    (long long)n_out);

@@ -199,7 +199,11 @@ int sgnn_rulebook_subm3_volume(const int32_t *coords, int64_t n, int dim_z, int 
  *   coarse_coords[c*4..]   coordinates of coarse row c   (room for nf rows)
  *   ckeys/cvals (ccap)     hash grid of the coarse level (key -> coarse row)
  *   *n_coarse (device)     number of coarse sites
- * ccap = sgnn_hash_capacity(nf). */
+ * ccap = sgnn_hash_capacity(nf).  Values of empty hash slots are unspecified; nf = 0 leaves an empty hash and count 0.
+ * This is sgnn_down2_chain at depth 1 with the row count on the host: 5 launches (6 with sgnn_tune.scan_inline = 0).
+ * Workspace (sgnn_down2_ws_bytes): slot and rank of every fine row, the owner table (ccap ints), the block sums.  The
+ * three *_ws_bytes queries of this section presume ccap = sgnn_hash_capacity(rows); a call with a larger ccap needs
+ * 4 * (ccap - sgnn_hash_capacity(rows)) more bytes per level slice and is refused (SGNN_ENOWS) without them. */
 int64_t sgnn_down2_ws_bytes(int64_t nf);
 int sgnn_rulebook_down2(const int32_t *fine_coords, int64_t nf, uint64_t *ckeys, int32_t *cvals,
                         int64_t ccap, int32_t *parent, int32_t *coarse_coords, int64_t *n_coarse,
@@ -222,7 +226,10 @@ int sgnn_down2_tables(const int32_t *fine_coords, const int32_t *parent, int64_t
  * are HOST arrays of device pointers.  Results are identical to `depth` calls of sgnn_rulebook_down2 (first-touch
  * order); the host reads all counts with one copy and then calls sgnn_down2_tables per level.
  * Capacity mode: level_caps (HOST array, depth entries, or NULL) clamps counts_dev[l] to the capacity of the buffers
- * that will hold level l+1's features and raises SGNN_STATUS_OVERFLOW in *status when it had to. */
+ * that will hold level l+1's features and raises SGNN_STATUS_OVERFLOW in *status when it had to.
+ * 5 launches per level (init, insert, count, write, parent), 6 with sgnn_tune.scan_inline = 0 (the scan of the block
+ * counts).  Workspace (sgnn_down2_chain_ws_bytes): the scratch of one level (slot and rank of `cap` rows, owner table
+ * of ccap ints, block sums), used by every level in turn. */
 int64_t sgnn_down2_chain_ws_bytes(int64_t cap);
 int sgnn_down2_chain(const int32_t *fine_coords, int64_t n0, const int64_t *n0_dev, int64_t cap, int depth,
                      void *const *ckeys, void *const *cvals, int64_t ccap, void *const *parent,
@@ -230,10 +237,12 @@ int sgnn_down2_chain(const int32_t *fine_coords, int64_t n0, const int64_t *n0_d
                      void *ws, int64_t ws_bytes, sgnn_stream_t stream);
 
 /* Capacity mode: the pyramid AND its tables in one submission — sgnn_down2_chain (row counts from *n0_dev, clamped to
- * level_caps, SGNN_STATUS_OVERFLOW) followed by sgnn_down2_tables of every level, as 3 launches per level + 2 (round 5: insert,
- * count, write kernel; the tables pass of a level shares a launch with the next level's insertion; 5 per level + 1 with
- * sgnn_tune.scan_inline = 0 / chain_merged = 0) instead of 8 per level.  children[l] is (8 x ldc_l), ldc_l = roundup256(min(level_caps[l], cap)); ptable[l] is (8 x ldf_l),
- * ldf_0 = roundup256(cap), ldf_l = ldc_{l-1}.  Only rows below roundup256(live count) of a table are written (and read). */
+ * level_caps, SGNN_STATUS_OVERFLOW) followed by sgnn_down2_tables of every level, as 3 launches per level + 2 (one init
+ * for all levels, the insertion of level 0; per level count, write kernel, parent + tables pass, which also runs the next
+ * level's insertion; 5 per level + 1 with sgnn_tune.scan_inline = 0 / chain_merged = 0) instead of 8 per level.
+ * children[l] is (8 x ldc_l), ldc_l = roundup256(min(level_caps[l], cap)); ptable[l] is (8 x ldf_l),
+ * ldf_0 = roundup256(cap), ldf_l = ldc_{l-1}.  Only rows below roundup256(live count) of a table are written (and read).
+ * Workspace (sgnn_down2_chain_tables_ws_bytes): sgnn_down2_chain's level scratch once per level, one set of block sums. */
 int64_t sgnn_down2_chain_tables_ws_bytes(int64_t cap, int depth);
 int sgnn_down2_chain_tables(const int32_t *fine_coords, const int64_t *n0_dev, int64_t cap, int depth,
                             void *const *ckeys, void *const *cvals, int64_t ccap, void *const *parent,

@@ -515,8 +515,8 @@ struct FlagDense {  // site i is kept iff a dense (B,1,d0,d1,d2) volume is > 0.5
 };
 struct FlagOwner {  // fine site i owns its parent iff it is the smallest row that touched it
   const int32_t *slot_of;
-  const int32_t *cvals;
-  __device__ __forceinline__ bool operator()(int64_t i) const { return cvals[slot_of[i]] == (int32_t)i; }
+  const int32_t *owner;
+  __device__ __forceinline__ bool operator()(int64_t i) const { return owner[slot_of[i]] == (int32_t)i; }
 };
 
 template <class F>
@@ -641,12 +641,27 @@ __global__ __launch_bounds__(1024) void k_scan_block_sums(int32_t *__restrict__ 
   }
 }
 
+// the ranked write of this workgroup's SCAN_BLOCK rows: a selected row i gets emit(i, running + selected rows in front of it
+// in the block); `running` = selected rows of the workgroups in front.  lds4: 4 ints of LDS.  Call from all threads.
+template <class F, class Emit>
+__device__ __forceinline__ void scan_emit_rows(const F &flag, const Emit &emit, int64_t n, int running, int *lds4) {
+  const int64_t base = (int64_t)blockIdx.x * SCAN_BLOCK;
+#pragma unroll 1
+  for (int it = 0; it < SCAN_ITEMS; ++it) {
+    const int64_t i = base + it * 256 + threadIdx.x;
+    const bool f = (i < n) && flag(i);
+    int total;
+    const int r = sgnn_block_rank256(f, lds4, total);
+    if (f) emit(i, running + r);
+    running += total;
+  }
+}
+
 template <class F, class Emit>
 __global__ __launch_bounds__(256) void k_scan_emit(F flag, Emit emit, int64_t n,
                                                   const int32_t *block_offsets, const int64_t *n_dev, ScanInline si) {
   n = sgnn_dyn_n(n, n_dev);
   __shared__ int lds[8];
-  const int64_t base = (int64_t)blockIdx.x * SCAN_BLOCK;
   int running;
   if (si.nblk > 0) {     // raw block sums: this workgroup's offset and the total, no scan launch (uniform over the launch)
     int64_t total;
@@ -655,15 +670,7 @@ __global__ __launch_bounds__(256) void k_scan_emit(F flag, Emit emit, int64_t n,
   } else {
     running = block_offsets[blockIdx.x];
   }
-#pragma unroll 1
-  for (int it = 0; it < SCAN_ITEMS; ++it) {
-    const int64_t i = base + it * 256 + threadIdx.x;
-    const bool f = (i < n) && flag(i);
-    int total;
-    const int r = sgnn_block_rank256(f, lds, total);
-    if (f) emit(i, running + r);
-    running += total;
-  }
+  scan_emit_rows(flag, emit, n, running, lds);
 }
 
 struct EmitSel {
@@ -794,134 +801,48 @@ SGNN_EXPORT int sgnn_compact_mask(const uint8_t *mask, int64_t n, int32_t *sel, 
 }
 
 // ---------------------------------------------------------------------------
-// stride-2 rulebook
+// stride-2 hierarchy (scn.Convolution(.., 2, 2)).  The sites of a coarse level are the distinct parents (coordinates >> 1)
+// of the fine level, in the order of their first-touch owners: the smallest fine row of each parent.  One level is
+//   init     coarse hash keys = empty, owner table = INT_MAX, ranks = -1                               k_chain_init(_all)
+//   insert   every fine row's parent into the coarse hash: owner[slot] = min row, slot_of[row] = slot  chain_insert_rows
+//   count    owners per 2048-row block, then their scan unless the write kernel sums the counts itself k_chain_count, k_scan_count<FlagOwner>
+//   write    the owners, in fine-row order, become the coarse rows: coordinates, rank_at[owner] = row  scan_emit_rows
+//   parent   parent[row] = rank_at[owner[slot_of[row]]], the hash's values become coarse rows, and
+//            (tables form) the row's children / ptable entries                                         chain_parent_rows
+// Every kernel takes its row count from device memory where the caller has one (the count the level above or a mask
+// compaction just wrote) and is launched for the host-known upper bound `cap`, so a pyramid needs no host round trip
+// between its levels.  The owner table is scratch of its own: the parent pass writes the hash's values while other
+// threads still read owners.  Values of empty hash slots are never written (no reader loads them: sgnn_hash_find and the
+// rulebook builders read a value only after its key matched).
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_down2_insert(const int4 *__restrict__ fine, int64_t nf,
-                                                     unsigned long long *__restrict__ ckeys,
-                                                     int32_t *__restrict__ cvals, uint64_t mask,
-                                                     int32_t *__restrict__ slot_of) {
-  int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  for (; i < nf; i += stride) {
-    const int4 c = fine[i];
-    const uint64_t key = sgnn_pack_key(c.x >> 1, c.y >> 1, c.z >> 1, c.w);
-    uint64_t slot = sgnn_hash64(key) & mask;
-    while (true) {
-      const unsigned long long prev = atomicCAS(&ckeys[slot], SGNN_EMPTY_KEY, (unsigned long long)key);
-      if (prev == SGNN_EMPTY_KEY || prev == key) break;
-      slot = (slot + 1) & mask;
-    }
-    atomicMin(&cvals[slot], (int32_t)i);  // first-touch owner = smallest fine row
-    slot_of[i] = (int32_t)slot;
-  }
-}
+#define CHAIN_MAX_DEPTH 8
 
-struct EmitOwner {  // owner i gets coarse row `rank`
-  const int4 *fine;
-  int4 *coarse;
-  int32_t *rank_at;
-  __device__ __forceinline__ void operator()(int64_t i, int rank) const {
-    const int4 c = fine[i];
-    coarse[rank] = make_int4(c.x >> 1, c.y >> 1, c.z >> 1, c.w);
-    rank_at[i] = rank;
-  }
+struct ChainScratch {   // per-level slice of the workspace
+  int32_t *slot_of, *rank_at, *owner;
 };
 
-__global__ __launch_bounds__(256) void k_down2_parent(int64_t nf, const int32_t *__restrict__ cvals,
-                                                     const int32_t *__restrict__ rank_at,
-                                                     const int32_t *__restrict__ slot_of,
-                                                     int32_t *__restrict__ parent) {
-  int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  for (; i < nf; i += stride) parent[i] = rank_at[cvals[slot_of[i]]];
+// `slices` level scratches (slot_of[cap] + rank_at[cap] + owner[ccap] each) + the block sums of one level at a time
+static int64_t chain_ws_bytes(int64_t cap, int64_t ccap, int slices) {
+  const int64_t nblk = (cap + SCAN_BLOCK - 1) / SCAN_BLOCK;
+  return (slices * (2 * cap + ccap) + nblk + 1) * (int64_t)sizeof(int32_t) + 256;
 }
 
-// after every parent[] is known: turn the coarse table's values from "owner fine row"
-// into "coarse row" so it is an ordinary grid hash for the next level
-__global__ __launch_bounds__(256) void k_down2_fix_vals(int64_t nf, const int32_t *__restrict__ slot_of,
-                                                       const int32_t *__restrict__ parent,
-                                                       const int32_t *__restrict__ rank_at,
-                                                       int32_t *__restrict__ cvals) {
-  int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  for (; i < nf; i += stride) {
-    // exactly one fine row per coarse site is its owner: cvals[slot] == i before this kernel.
-    // Owners are identified through rank_at (written only for owners, -1 elsewhere).
-    if (rank_at[i] >= 0) cvals[slot_of[i]] = parent[i];
-  }
+// -> the block sums behind the slices
+static int32_t *chain_ws_carve(void *ws, int64_t cap, int64_t ccap, int slices, ChainScratch *w) {
+  int32_t *p = (int32_t *)ws;
+  for (int l = 0; l < slices; ++l, p += 2 * cap + ccap) w[l] = ChainScratch{p, p + cap, p + 2 * cap};
+  return p;
 }
 
-SGNN_EXPORT int64_t sgnn_down2_ws_bytes(int64_t nf) {
-  const int64_t nblk = (nf + SCAN_BLOCK - 1) / SCAN_BLOCK;
-  // slot_of[nf] + rank_at[nf] + block sums
-  return 2 * nf * (int64_t)sizeof(int32_t) + (nblk + 1) * (int64_t)sizeof(int32_t) + 256;
-}
+struct ChainInit {
+  unsigned long long *ckeys[CHAIN_MAX_DEPTH];
+  int32_t *owner[CHAIN_MAX_DEPTH];
+  int32_t *rank_at[CHAIN_MAX_DEPTH];
+  int64_t ccap, cap;
+};
 
-// one launch initialises the coarse hash (keys = empty, values = INT_MAX) and the rank scratch (-1)
-__global__ __launch_bounds__(256) void k_down2_init(unsigned long long *__restrict__ ckeys, int32_t *__restrict__ cvals,
-                                                   int64_t ccap, int32_t *__restrict__ rank_at, int64_t nf) {
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  const int64_t top = ccap > nf ? ccap : nf;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < top; i += stride) {
-    if (i < ccap) {
-      ckeys[i] = ~0ull;
-      cvals[i] = 0x7FFFFFFF;
-    }
-    if (i < nf) rank_at[i] = -1;
-  }
-}
-
-SGNN_EXPORT int sgnn_rulebook_down2(const int32_t *fine_coords, int64_t nf, uint64_t *ckeys, int32_t *cvals,
-                                    int64_t ccap, int32_t *parent, int32_t *coarse_coords,
-                                    int64_t *n_coarse, void *ws, int64_t ws_bytes, sgnn_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  SGNN_CHECK_ARG(nf >= 0 && n_coarse && ckeys && cvals);
-  SGNN_CHECK_ARG(ccap >= 2 * nf && ccap >= 2 && (ccap & (ccap - 1)) == 0 && ccap < (1ll << 31));
-  if (nf == 0) {
-    SGNN_HIP_TRY(hipMemsetAsync(ckeys, 0xFF, (size_t)ccap * sizeof(uint64_t), s));
-    SGNN_HIP_TRY(hipMemsetAsync(n_coarse, 0, sizeof(int64_t), s));
-    return SGNN_OK;
-  }
-  SGNN_CHECK_ARG(fine_coords && parent && coarse_coords);
-  if (!ws || ws_bytes < sgnn_down2_ws_bytes(nf)) {
-    sgnn_set_error("sgnn_rulebook_down2: workspace too small");
-    return SGNN_ENOWS;
-  }
-  const int64_t nblk = (nf + SCAN_BLOCK - 1) / SCAN_BLOCK;
-  int32_t *slot_of = (int32_t *)ws;
-  int32_t *rank_at = slot_of + nf;
-  int32_t *block_sums = rank_at + nf;
-  SGNN_LAUNCH(k_down2_init, dim3(sgnn_grid_for(ccap, 256, 4096)), dim3(256), 0, s, (unsigned long long *)ckeys,
-                     cvals, ccap, rank_at, nf);
-  const int g = sgnn_grid_for(nf, 256, 8192);
-  SGNN_LAUNCH(k_down2_insert, dim3(g), dim3(256), 0, s, (const int4 *)fine_coords, nf,
-                     (unsigned long long *)ckeys, cvals, (uint64_t)(ccap - 1), slot_of);
-  FlagOwner flag{slot_of, cvals};
-  SGNN_LAUNCH((k_scan_count<FlagOwner>), dim3((unsigned)nblk), dim3(256), 0, s, flag, nf, block_sums,
-                     (const int64_t *)nullptr);
-  const bool inl = scan_inline_ok(nblk);
-  if (!inl) SGNN_LAUNCH(k_scan_block_sums, dim3(1), dim3(1024), 0, s, block_sums, nblk, n_coarse, kNoLimit);
-  SGNN_LAUNCH((k_scan_emit<FlagOwner, EmitOwner>), dim3((unsigned)nblk), dim3(256), 0, s, flag,
-                     EmitOwner{(const int4 *)fine_coords, (int4 *)coarse_coords, rank_at}, nf,
-                     (const int32_t *)block_sums, (const int64_t *)nullptr,
-                     inl ? ScanInline{nblk, n_coarse, kNoLimit} : kNoInline);
-  SGNN_LAUNCH(k_down2_parent, dim3(g), dim3(256), 0, s, nf, (const int32_t *)cvals,
-                     (const int32_t *)rank_at, (const int32_t *)slot_of, parent);
-  SGNN_LAUNCH(k_down2_fix_vals, dim3(g), dim3(256), 0, s, nf, (const int32_t *)slot_of,
-                     (const int32_t *)parent, (const int32_t *)rank_at, cvals);
-  SGNN_CHECK_LAUNCH();
-  return SGNN_OK;
-}
-
-// ---------------------------------------------------------------------------
-// stride-2 rulebooks of several successive levels WITHOUT a host round trip in between: every kernel takes its row
-// count from device memory (the count the previous level / a mask compaction just wrote) and is launched for the
-// host-known upper bound `cap`.  One read-back then returns all counts (15 -> 5 host syncs per training step).
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ int64_t dev_n(const int64_t *n_dev, int64_t n_host) { return sgnn_dyn_n(n_host, n_dev); }
-
-__global__ __launch_bounds__(256) void k_chain_init(unsigned long long *__restrict__ ckeys, int32_t *__restrict__ owner,
-                                                   int64_t ccap, int32_t *__restrict__ rank_at, int64_t cap) {
+__device__ __forceinline__ void chain_init_rows(unsigned long long *__restrict__ ckeys, int32_t *__restrict__ owner,
+                                                int64_t ccap, int32_t *__restrict__ rank_at, int64_t cap) {
   const int64_t stride = (int64_t)gridDim.x * 256;
   const int64_t top = ccap > cap ? ccap : cap;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < top; i += stride) {
@@ -933,11 +854,25 @@ __global__ __launch_bounds__(256) void k_chain_init(unsigned long long *__restri
   }
 }
 
+// The eager pyramid (down2_chain) launches its init, count, write and parent passes through kernels with plain pointer
+// arguments: k_chain_init, k_chain_count, k_chain_emit, k_chain_parent.  Launched through the struct-argument forms of
+// the capacity path instead (k_chain_init_all, k_scan_count / k_scan_emit<FlagOwner ..>, k_chain_parent_tables), the same
+// loops measured 1 - 2 us more per three-level pyramid, in the gaps between the launches (profiles/down2_refactor.json).
+__global__ __launch_bounds__(256) void k_chain_init(unsigned long long *__restrict__ ckeys, int32_t *__restrict__ owner,
+                                                   int64_t ccap, int32_t *__restrict__ rank_at, int64_t cap) {
+  chain_init_rows(ckeys, owner, ccap, rank_at, cap);
+}
+
+// grid (x, levels): blockIdx.y is the level
+__global__ __launch_bounds__(256) void k_chain_init_all(ChainInit a) {
+  chain_init_rows(a.ckeys[blockIdx.y], a.owner[blockIdx.y], a.ccap, a.rank_at[blockIdx.y], a.cap);
+}
+
 __device__ __forceinline__ void chain_insert_rows(const int4 *__restrict__ fine, const int64_t *n_dev, int64_t n_host,
                                                   unsigned long long *__restrict__ ckeys,
                                                   int32_t *__restrict__ owner, uint64_t mask,
                                                   int32_t *__restrict__ slot_of) {
-  const int64_t nf = dev_n(n_dev, n_host);
+  const int64_t nf = sgnn_dyn_n(n_host, n_dev);
   int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (; i < nf; i += stride) {
@@ -961,11 +896,23 @@ __global__ __launch_bounds__(256) void k_chain_insert(const int4 *__restrict__ f
   chain_insert_rows(fine, n_dev, n_host, ckeys, owner, mask, slot_of);
 }
 
+struct EmitOwner {  // owner i gets coarse row `rank`
+  const int4 *fine;
+  int4 *coarse;
+  int32_t *rank_at;
+  __device__ __forceinline__ void operator()(int64_t i, int rank) const {
+    const int4 c = fine[i];
+    coarse[rank] = make_int4(c.x >> 1, c.y >> 1, c.z >> 1, c.w);
+    rank_at[i] = rank;
+  }
+};
+
+// k_scan_count<FlagOwner> and k_scan_emit<FlagOwner, EmitOwner> with plain arguments
 __global__ __launch_bounds__(256) void k_chain_count(const int32_t *__restrict__ slot_of, const int32_t *__restrict__ owner,
                                                     const int64_t *n_dev, int64_t n_host,
                                                     int32_t *__restrict__ block_sums) {
   __shared__ int lds[4];
-  const int64_t n = dev_n(n_dev, n_host);
+  const int64_t n = sgnn_dyn_n(n_host, n_dev);
   const int64_t base = (int64_t)blockIdx.x * SCAN_BLOCK;
   int cnt = 0;
 #pragma unroll
@@ -979,14 +926,12 @@ __global__ __launch_bounds__(256) void k_chain_count(const int32_t *__restrict__
   if (threadIdx.x == 0) block_sums[blockIdx.x] = lds[0] + lds[1] + lds[2] + lds[3];
 }
 
-// owners, in fine-row order, become the coarse rows: coordinates and rank
 __global__ __launch_bounds__(256) void k_chain_emit(const int4 *__restrict__ fine, const int32_t *__restrict__ slot_of,
                                                    const int32_t *__restrict__ owner, const int64_t *n_dev,
                                                    int64_t n_host, const int32_t *block_offsets,
                                                    int4 *__restrict__ coarse, int32_t *__restrict__ rank_at, ScanInline si) {
   __shared__ int lds[8];
-  const int64_t n = dev_n(n_dev, n_host);
-  const int64_t base = (int64_t)blockIdx.x * SCAN_BLOCK;
+  const int64_t n = sgnn_dyn_n(n_host, n_dev);
   int running;
   if (si.nblk > 0) {
     int64_t total;
@@ -995,131 +940,10 @@ __global__ __launch_bounds__(256) void k_chain_emit(const int4 *__restrict__ fin
   } else {
     running = block_offsets[blockIdx.x];
   }
-#pragma unroll 1
-  for (int it = 0; it < SCAN_ITEMS; ++it) {
-    const int64_t i = base + it * 256 + threadIdx.x;
-    const bool f = (i < n) && owner[slot_of[i]] == (int32_t)i;
-    int total;
-    const int r = sgnn_block_rank256(f, lds, total);
-    if (f) {
-      const int4 c = fine[i];
-      coarse[running + r] = make_int4(c.x >> 1, c.y >> 1, c.z >> 1, c.w);
-      rank_at[i] = running + r;
-    }
-    running += total;
-  }
+  scan_emit_rows(FlagOwner{slot_of, owner}, EmitOwner{fine, coarse, rank_at}, n, running, lds);
 }
 
-// parent row of every fine site; the coarse hash's values become coarse rows (written by the owners into cvals, a
-// different array than the owner table the other threads are still reading)
-__global__ __launch_bounds__(256) void k_chain_parent(const int64_t *n_dev, int64_t n_host,
-                                                     const int32_t *__restrict__ owner,
-                                                     const int32_t *__restrict__ rank_at,
-                                                     const int32_t *__restrict__ slot_of,
-                                                     int32_t *__restrict__ parent, int32_t *__restrict__ cvals) {
-  const int64_t nf = dev_n(n_dev, n_host);
-  int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  for (; i < nf; i += stride) {
-    const int32_t sl = slot_of[i];
-    const int32_t p = rank_at[owner[sl]];
-    parent[i] = p;
-    if (rank_at[i] >= 0) cvals[sl] = p;
-  }
-}
-
-SGNN_EXPORT int64_t sgnn_down2_chain_ws_bytes(int64_t cap) {
-  const int64_t nblk = (cap + SCAN_BLOCK - 1) / SCAN_BLOCK;
-  // slot_of[cap] + rank_at[cap] + owner[ccap] + block sums
-  return (2 * cap + sgnn_hash_capacity(cap)) * (int64_t)sizeof(int32_t) + (nblk + 1) * (int64_t)sizeof(int32_t) + 256;
-}
-
-SGNN_EXPORT int sgnn_down2_chain(const int32_t *fine_coords, int64_t n0, const int64_t *n0_dev, int64_t cap, int depth,
-                                 void *const *ckeys, void *const *cvals, int64_t ccap, void *const *parent,
-                                 void *const *coarse_coords, int64_t *counts_dev, const int64_t *level_caps,
-                                 int32_t *status, void *ws, int64_t ws_bytes, sgnn_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  SGNN_CHECK_ARG(!level_caps || status);
-  SGNN_CHECK_ARG(depth >= 1 && depth <= 8 && cap >= 0 && n0 >= 0 && n0 <= cap && counts_dev && ckeys && cvals && parent &&
-                 coarse_coords);
-  SGNN_CHECK_ARG(ccap >= 2 * cap && ccap >= 2 && (ccap & (ccap - 1)) == 0 && ccap < (1ll << 31));
-  if (cap == 0) {
-    SGNN_HIP_TRY(hipMemsetAsync(counts_dev, 0, depth * sizeof(int64_t), s));
-    for (int l = 0; l < depth; ++l) SGNN_HIP_TRY(hipMemsetAsync(ckeys[l], 0xFF, (size_t)ccap * sizeof(uint64_t), s));
-    return SGNN_OK;
-  }
-  SGNN_CHECK_ARG(fine_coords);
-  if (!ws || ws_bytes < sgnn_down2_chain_ws_bytes(cap)) {
-    sgnn_set_error("sgnn_down2_chain: workspace too small");
-    return SGNN_ENOWS;
-  }
-  const int64_t nblk = (cap + SCAN_BLOCK - 1) / SCAN_BLOCK;
-  int32_t *slot_of = (int32_t *)ws;
-  int32_t *rank_at = slot_of + cap;
-  int32_t *owner = rank_at + cap;
-  int32_t *block_sums = owner + ccap;
-  const int4 *fine = (const int4 *)fine_coords;
-  const int64_t *n_dev = n0_dev;
-  int64_t n_host = n0_dev ? cap : n0;
-  const int g = sgnn_grid_for(cap, 256, 8192);
-  for (int l = 0; l < depth; ++l) {
-    SGNN_CHECK_ARG(ckeys[l] && cvals[l] && parent[l] && coarse_coords[l]);
-    SGNN_LAUNCH(k_chain_init, dim3(sgnn_grid_for(ccap, 256, 4096)), dim3(256), 0, s,
-                       (unsigned long long *)ckeys[l], owner, ccap, rank_at, cap);
-    SGNN_LAUNCH(k_chain_insert, dim3(g), dim3(256), 0, s, fine, n_dev, n_host, (unsigned long long *)ckeys[l],
-                       owner, (uint64_t)(ccap - 1), slot_of);
-    SGNN_LAUNCH(k_chain_count, dim3((unsigned)nblk), dim3(256), 0, s, (const int32_t *)slot_of,
-                       (const int32_t *)owner, n_dev, n_host, block_sums);
-    const ScanLimit lim = level_caps ? ScanLimit{level_caps[l] < cap ? level_caps[l] : cap, nullptr, 0, status} : kNoLimit;
-    const bool inl = scan_inline_ok(nblk);
-    if (!inl) SGNN_LAUNCH(k_scan_block_sums, dim3(1), dim3(1024), 0, s, block_sums, nblk, counts_dev + l, lim);
-    SGNN_LAUNCH(k_chain_emit, dim3((unsigned)nblk), dim3(256), 0, s, fine, (const int32_t *)slot_of,
-                       (const int32_t *)owner, n_dev, n_host, (const int32_t *)block_sums, (int4 *)coarse_coords[l],
-                       rank_at, inl ? ScanInline{nblk, counts_dev + l, lim} : kNoInline);
-    SGNN_LAUNCH(k_chain_parent, dim3(g), dim3(256), 0, s, n_dev, n_host, (const int32_t *)owner,
-                       (const int32_t *)rank_at, (const int32_t *)slot_of, (int32_t *)parent[l], (int32_t *)cvals[l]);
-    fine = (const int4 *)coarse_coords[l];
-    n_dev = counts_dev + l;
-    n_host = cap;
-  }
-  SGNN_CHECK_LAUNCH();
-  return SGNN_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Capacity mode: the whole stride-2 pyramid INCLUDING its children / ptable tables in one submission with 5 launches
-// per level + 1 per chain (the step-by-step form above needs 8 per level: init, insert, count, scan, emit, parent,
-// children pre-fill, tables) — 3 per level + 2 since round 5: the write kernel sums the block counts itself (no scan
-// launch, scan_offsets_inline) and the tables pass of level l shares a launch with the insertion of level l + 1:
-//   k_chain_init_all   every level's hash / owner / rank scratch (each level has its own scratch slice)
-//   per level: k_chain_insert, k_chain_count, k_scan_block_sums (clamps to the level capacity),
-//              k_chain_emit2 (also pre-fills the children table up to the live coarse rows),
-//              k_chain_parent_tables (parent[], coarse hash values, children[], ptable[])
-// Same first-touch order, same tables as sgnn_down2_chain + sgnn_down2_tables (tests/test_gpu_capacity.py).
-// ---------------------------------------------------------------------------
-#define CHAIN_MAX_DEPTH 8
-struct ChainInit {
-  unsigned long long *ckeys[CHAIN_MAX_DEPTH];
-  int32_t *owner[CHAIN_MAX_DEPTH];
-  int32_t *rank_at[CHAIN_MAX_DEPTH];
-  int64_t ccap, cap;
-  int depth;
-};
-
-__global__ __launch_bounds__(256) void k_chain_init_all(ChainInit a) {
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  const int64_t top = a.ccap > a.cap ? a.ccap : a.cap;
-  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < top * a.depth; g += stride) {
-    const int l = (int)(g / top);
-    const int64_t i = g - (int64_t)l * top;
-    if (i < a.ccap) {
-      a.ckeys[l][i] = ~0ull;
-      a.owner[l][i] = 0x7FFFFFFF;
-    }
-    if (i < a.cap) a.rank_at[l][i] = -1;
-  }
-}
-
+// k_scan_emit<FlagOwner, EmitOwner> that also pre-fills the children table of the coarse level up to its live rows
 __global__ __launch_bounds__(256) void k_chain_emit2(const int4 *__restrict__ fine, const int32_t *__restrict__ slot_of,
                                                     const int32_t *__restrict__ owner, const int64_t *n_dev,
                                                     int64_t n_host, const int32_t *block_offsets,
@@ -1127,7 +951,7 @@ __global__ __launch_bounds__(256) void k_chain_emit2(const int4 *__restrict__ fi
                                                     const int64_t *nc_dev, int32_t *__restrict__ children, int64_t ldc,
                                                     ScanInline si) {
   __shared__ int lds[8];
-  const int64_t n = dev_n(n_dev, n_host);
+  const int64_t n = sgnn_dyn_n(n_host, n_dev);
   int running = 0;
   int64_t nc_live;
   if (si.nblk > 0) {     // raw block sums: offset, total and the clamped live count of the coarse level from this workgroup's own sum
@@ -1143,25 +967,32 @@ __global__ __launch_bounds__(256) void k_chain_emit2(const int4 *__restrict__ fi
     const int64_t total = end * 8, stride = (int64_t)gridDim.x * 256;
     for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < total; g += stride) children[(g / end) * ldc + (g % end)] = -1;
   }
-  const int64_t base = (int64_t)blockIdx.x * SCAN_BLOCK;
-  if (base >= n) return;
+  if ((int64_t)blockIdx.x * SCAN_BLOCK >= n) return;
   if (si.nblk <= 0) running = block_offsets[blockIdx.x];
-#pragma unroll 1
-  for (int it = 0; it < SCAN_ITEMS; ++it) {
-    const int64_t i = base + it * 256 + threadIdx.x;
-    const bool f = (i < n) && owner[slot_of[i]] == (int32_t)i;
-    int total;
-    const int r = sgnn_block_rank256(f, lds, total);
-    if (f) {
-      const int4 c = fine[i];
-      coarse[running + r] = make_int4(c.x >> 1, c.y >> 1, c.z >> 1, c.w);
-      rank_at[i] = running + r;
-    }
-    running += total;
-  }
+  scan_emit_rows(FlagOwner{slot_of, owner}, EmitOwner{fine, coarse, rank_at}, n, running, lds);
 }
 
-struct ChainTables {   // arguments of the parent / children / ptable pass of one level
+// Entries of fine row i in the two offset-major tables of its level, p = its parent: children[off][p] = i and
+// ptable[off][i] = p at the site's parity offset, ptable = -1 at the seven others.  A parent at or beyond the nc rows the
+// coarse level keeps (only after a capacity overflow: the step is flagged and discarded) counts as absent, so every
+// entry stays in bounds; Record: parent[i] := p as entered.  A padding row (pad; p = -1) is all -1.
+template <bool Record>
+__device__ __forceinline__ void down2_table_row(int64_t i, bool pad, const int4 *__restrict__ fine, int32_t p, int64_t nc,
+                                                int32_t *__restrict__ parent, int32_t *__restrict__ children, int64_t ldc,
+                                                int32_t *__restrict__ ptable, int64_t ldf) {
+  int off = -1;
+  if (!pad) {
+    if (p >= nc) p = -1;
+    if (Record) parent[i] = p;
+    const int4 c = fine[i];
+    off = ((c.x & 1) << 2) | ((c.y & 1) << 1) | (c.z & 1);
+    if (p >= 0) children[(int64_t)off * ldc + p] = (int32_t)i;
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) ptable[(int64_t)k * ldf + i] = (k == off) ? p : -1;
+}
+
+struct ChainTables {   // arguments of the parent + tables pass of one level
   const int4 *fine;
   const int64_t *n_dev;
   int64_t n_host;
@@ -1175,62 +1006,170 @@ struct ChainTables {   // arguments of the parent / children / ptable pass of on
   int64_t ldf;
 };
 
-__device__ __forceinline__ void chain_parent_tables_rows(const int4 *__restrict__ fine, const int64_t *n_dev,
-                                                         int64_t n_host, const int32_t *__restrict__ owner,
-                                                         const int32_t *__restrict__ rank_at,
-                                                         const int32_t *__restrict__ slot_of,
-                                                         int32_t *__restrict__ parent, int32_t *__restrict__ cvals,
-                                                         const int64_t *nc_dev, int64_t nc_cap,
-                                                         int32_t *__restrict__ children, int64_t ldc,
-                                                         int32_t *__restrict__ ptable, int64_t ldf) {
-  const int64_t nf = dev_n(n_dev, n_host);
-  const int64_t nc = sgnn_dyn_n(nc_cap, nc_dev);
-  const int64_t iend = pad_end(nf, ldf);
+// parent row of every fine site; the owners also turn the coarse hash's values into coarse rows (the true row even past
+// a clamped capacity).  Tables: the children / ptable entries as well, padding rows included, and parent[] as entered there.
+template <bool Tables>
+__device__ __forceinline__ void chain_parent_rows(const int4 *__restrict__ fine, const int64_t *n_dev, int64_t n_host,
+                                                  const int32_t *__restrict__ owner,
+                                                  const int32_t *__restrict__ rank_at,
+                                                  const int32_t *__restrict__ slot_of,
+                                                  int32_t *__restrict__ parent, int32_t *__restrict__ cvals,
+                                                  const int64_t *nc_dev, int64_t nc_cap,
+                                                  int32_t *__restrict__ children, int64_t ldc,
+                                                  int32_t *__restrict__ ptable, int64_t ldf) {
+  const int64_t nf = sgnn_dyn_n(n_host, n_dev);
+  const int64_t nc = Tables ? sgnn_dyn_n(nc_cap, nc_dev) : 0;
+  const int64_t iend = Tables ? pad_end(nf, ldf) : nf;
   int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (; i < iend; i += stride) {
-    if (i >= nf) {  // padding rows of the data-gradient table
-#pragma unroll
-      for (int k = 0; k < 8; ++k) ptable[(int64_t)k * ldf + i] = -1;
+    if (Tables && i >= nf) {  // padding rows of the data-gradient table
+      down2_table_row<false>(i, true, fine, -1, nc, nullptr, children, ldc, ptable, ldf);
       continue;
     }
     const int32_t sl = slot_of[i];
-    int32_t p = rank_at[owner[sl]];
-    if (rank_at[i] >= 0) cvals[sl] = p;      // the coarse hash keeps the true row even past a clamped capacity
-    if (p >= nc) p = -1;                      // only after a capacity overflow (the step is flagged and discarded)
-    parent[i] = p;
-    const int4 c = fine[i];
-    const int off = ((c.x & 1) << 2) | ((c.y & 1) << 1) | (c.z & 1);
-    if (p >= 0) children[(int64_t)off * ldc + p] = (int32_t)i;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) ptable[(int64_t)k * ldf + i] = (k == off) ? p : -1;
+    const int32_t p = rank_at[owner[sl]];
+    if (rank_at[i] >= 0) cvals[sl] = p;
+    if (Tables) down2_table_row<true>(i, false, fine, p, nc, parent, children, ldc, ptable, ldf);
+    else parent[i] = p;
   }
 }
 
-__global__ __launch_bounds__(256) void k_chain_parent_tables(ChainTables t) {
-  chain_parent_tables_rows(t.fine, t.n_dev, t.n_host, t.owner, t.rank_at, t.slot_of, t.parent, t.cvals, t.nc_dev, t.nc_cap,
-                           t.children, t.ldc, t.ptable, t.ldf);
+__global__ __launch_bounds__(256) void k_chain_parent(const int64_t *n_dev, int64_t n_host,
+                                                     const int32_t *__restrict__ owner,
+                                                     const int32_t *__restrict__ rank_at,
+                                                     const int32_t *__restrict__ slot_of,
+                                                     int32_t *__restrict__ parent, int32_t *__restrict__ cvals) {
+  chain_parent_rows<false>(nullptr, n_dev, n_host, owner, rank_at, slot_of, parent, cvals, nullptr, 0, nullptr, 0, nullptr, 0);
 }
 
-// Round 5: the tables pass of level l and the hash insertion of level l + 1 both wait for level l's write kernel only
-// (coarse coordinates + count, ranks) and touch disjoint arrays — one launch runs both loops (a launch less per inner level).
+__global__ __launch_bounds__(256) void k_chain_parent_tables(ChainTables t) {
+  chain_parent_rows<true>(t.fine, t.n_dev, t.n_host, t.owner, t.rank_at, t.slot_of, t.parent, t.cvals, t.nc_dev, t.nc_cap,
+                          t.children, t.ldc, t.ptable, t.ldf);
+}
+
+// the tables pass of level l and the hash insertion of level l + 1 both wait for level l's write kernel only (coarse
+// coordinates + count, ranks) and touch disjoint arrays: one launch runs both loops (a launch less per inner level)
 __global__ __launch_bounds__(256) void k_chain_tables_insert(ChainTables t, unsigned long long *__restrict__ ckeys_next,
                                                             int32_t *__restrict__ owner_next, uint64_t mask,
                                                             int32_t *__restrict__ slot_of_next, const int4 *coarse,
                                                             int64_t n_host_next) {
-  chain_parent_tables_rows(t.fine, t.n_dev, t.n_host, t.owner, t.rank_at, t.slot_of, t.parent, t.cvals, t.nc_dev, t.nc_cap,
-                           t.children, t.ldc, t.ptable, t.ldf);
+  chain_parent_rows<true>(t.fine, t.n_dev, t.n_host, t.owner, t.rank_at, t.slot_of, t.parent, t.cvals, t.nc_dev, t.nc_cap,
+                          t.children, t.ldc, t.ptable, t.ldf);
   chain_insert_rows(coarse, t.nc_dev, n_host_next, ckeys_next, owner_next, mask, slot_of_next);
 }
 
-
-SGNN_EXPORT int64_t sgnn_down2_chain_tables_ws_bytes(int64_t cap, int depth) {
-  const int64_t nblk = (cap + SCAN_BLOCK - 1) / SCAN_BLOCK;
-  return depth * (2 * cap + sgnn_hash_capacity(cap)) * (int64_t)sizeof(int32_t) + (nblk + 1) * (int64_t)sizeof(int32_t) + 256;
+// host side: the launches the entry points below share
+static void chain_launch_init(const ChainInit &ini, int levels, hipStream_t s) {
+  SGNN_LAUNCH(k_chain_init_all, dim3(sgnn_grid_for(ini.ccap, 256, 4096), levels), dim3(256), 0, s, ini);
 }
 
-// level l: fine rows = level_ld[l] stride tables; children[l] is (8 x ldc[l]) with ldc[l] = roundup256(level_caps[l]),
-// ptable[l] is (8 x ldf[l]) with ldf[0] = roundup256(cap), ldf[l] = ldc[l-1].  All pointer arrays are HOST arrays.
+static void chain_launch_insert(const int4 *fine, const int64_t *n_dev, int64_t n_host, int64_t cap, void *ckeys,
+                                const ChainScratch &w, int64_t ccap, hipStream_t s) {
+  SGNN_LAUNCH(k_chain_insert, dim3(sgnn_grid_for(cap, 256, 8192)), dim3(256), 0, s, fine, n_dev, n_host,
+              (unsigned long long *)ckeys, w.owner, (uint64_t)(ccap - 1), w.slot_of);
+}
+
+// owners per block and, unless the write kernel will sum them itself, their scan and the clamped total
+// -> what that write kernel gets as its ScanInline
+static ScanInline chain_launch_count(const ChainScratch &w, const int64_t *n_dev, int64_t n_host, int64_t cap,
+                                     int32_t *block_sums, int64_t *count, const ScanLimit &lim, hipStream_t s) {
+  const int64_t nblk = (cap + SCAN_BLOCK - 1) / SCAN_BLOCK;
+  SGNN_LAUNCH((k_scan_count<FlagOwner>), dim3((unsigned)nblk), dim3(256), 0, s, FlagOwner{w.slot_of, w.owner}, n_host,
+              block_sums, n_dev);
+  if (scan_inline_ok(nblk)) return ScanInline{nblk, count, lim};
+  SGNN_LAUNCH(k_scan_block_sums, dim3(1), dim3(1024), 0, s, block_sums, nblk, count, lim);
+  return kNoInline;
+}
+
+SGNN_EXPORT int64_t sgnn_down2_ws_bytes(int64_t nf) { return chain_ws_bytes(nf, sgnn_hash_capacity(nf), 1); }
+SGNN_EXPORT int64_t sgnn_down2_chain_ws_bytes(int64_t cap) { return chain_ws_bytes(cap, sgnn_hash_capacity(cap), 1); }
+SGNN_EXPORT int64_t sgnn_down2_chain_tables_ws_bytes(int64_t cap, int depth) {
+  return chain_ws_bytes(cap, sgnn_hash_capacity(cap), depth);
+}
+
+static int chain_hip_result(const char *who, hipError_t e) {
+  if (e == hipSuccess) return SGNN_OK;
+  sgnn_set_error("%s: HIP error: %s", who, hipGetErrorString(e));
+  return SGNN_EHIP;
+}
+
+// The pyramid without tables, 5 launches per level (6 with sgnn_tune.scan_inline = 0): init, insert, count, (scan,) write,
+// parent.  One scratch slice serves every level in turn.  `who`: the entry point, for its error texts.
+static int down2_chain(const char *who, const int32_t *fine_coords, int64_t n0, const int64_t *n0_dev, int64_t cap,
+                       int depth, void *const *ckeys, void *const *cvals, int64_t ccap, void *const *parent,
+                       void *const *coarse_coords, int64_t *counts_dev, const int64_t *level_caps, int32_t *status,
+                       void *ws, int64_t ws_bytes, hipStream_t s) {
+  if (cap == 0) {     // no sites: every level is an empty hash with count 0
+    hipError_t e = hipMemsetAsync(counts_dev, 0, depth * sizeof(int64_t), s);
+    for (int l = 0; l < depth && e == hipSuccess; ++l) e = hipMemsetAsync(ckeys[l], 0xFF, (size_t)ccap * sizeof(uint64_t), s);
+    return chain_hip_result(who, e);
+  }
+  if (!ws || ws_bytes < chain_ws_bytes(cap, ccap, 1)) {
+    sgnn_set_error("%s: workspace too small", who);
+    return SGNN_ENOWS;
+  }
+  ChainScratch w;
+  int32_t *block_sums = chain_ws_carve(ws, cap, ccap, 1, &w);
+  const int4 *fine = (const int4 *)fine_coords;
+  const int64_t *n_dev = n0_dev;
+  int64_t n_host = n0_dev ? cap : n0;
+  const int64_t nblk = (cap + SCAN_BLOCK - 1) / SCAN_BLOCK;
+  const int g = sgnn_grid_for(cap, 256, 8192);
+  const bool inl = scan_inline_ok(nblk);
+  for (int l = 0; l < depth; ++l) {
+    SGNN_LAUNCH(k_chain_init, dim3(sgnn_grid_for(ccap, 256, 4096)), dim3(256), 0, s, (unsigned long long *)ckeys[l],
+                w.owner, ccap, w.rank_at, cap);
+    chain_launch_insert(fine, n_dev, n_host, cap, ckeys[l], w, ccap, s);
+    SGNN_LAUNCH(k_chain_count, dim3((unsigned)nblk), dim3(256), 0, s, (const int32_t *)w.slot_of,
+                (const int32_t *)w.owner, n_dev, n_host, block_sums);
+    const ScanLimit lim = level_caps ? ScanLimit{level_caps[l] < cap ? level_caps[l] : cap, nullptr, 0, status} : kNoLimit;
+    if (!inl) SGNN_LAUNCH(k_scan_block_sums, dim3(1), dim3(1024), 0, s, block_sums, nblk, counts_dev + l, lim);
+    SGNN_LAUNCH(k_chain_emit, dim3((unsigned)nblk), dim3(256), 0, s, fine, (const int32_t *)w.slot_of,
+                (const int32_t *)w.owner, n_dev, n_host, (const int32_t *)block_sums, (int4 *)coarse_coords[l], w.rank_at,
+                inl ? ScanInline{nblk, counts_dev + l, lim} : kNoInline);
+    SGNN_LAUNCH(k_chain_parent, dim3(g), dim3(256), 0, s, n_dev, n_host, (const int32_t *)w.owner,
+                (const int32_t *)w.rank_at, (const int32_t *)w.slot_of, (int32_t *)parent[l], (int32_t *)cvals[l]);
+    fine = (const int4 *)coarse_coords[l];
+    n_dev = counts_dev + l;
+    n_host = cap;
+  }
+  return chain_hip_result(who, hipGetLastError());
+}
+
+// one level, row count known to the host: the pyramid at depth 1
+SGNN_EXPORT int sgnn_rulebook_down2(const int32_t *fine_coords, int64_t nf, uint64_t *ckeys, int32_t *cvals,
+                                    int64_t ccap, int32_t *parent, int32_t *coarse_coords,
+                                    int64_t *n_coarse, void *ws, int64_t ws_bytes, sgnn_stream_t stream) {
+  SGNN_CHECK_ARG(nf >= 0 && n_coarse && ckeys && cvals);
+  SGNN_CHECK_ARG(ccap >= 2 * nf && ccap >= 2 && (ccap & (ccap - 1)) == 0 && ccap < (1ll << 31));
+  SGNN_CHECK_ARG(nf == 0 || (fine_coords && parent && coarse_coords));
+  void *const k = ckeys, *const v = cvals, *const p = parent, *const c = coarse_coords;
+  return down2_chain("sgnn_rulebook_down2", fine_coords, nf, nullptr, nf, 1, &k, &v, ccap, &p, &c, n_coarse, nullptr,
+                     nullptr, ws, ws_bytes, (hipStream_t)stream);
+}
+
+SGNN_EXPORT int sgnn_down2_chain(const int32_t *fine_coords, int64_t n0, const int64_t *n0_dev, int64_t cap, int depth,
+                                 void *const *ckeys, void *const *cvals, int64_t ccap, void *const *parent,
+                                 void *const *coarse_coords, int64_t *counts_dev, const int64_t *level_caps,
+                                 int32_t *status, void *ws, int64_t ws_bytes, sgnn_stream_t stream) {
+  SGNN_CHECK_ARG(!level_caps || status);
+  SGNN_CHECK_ARG(depth >= 1 && depth <= CHAIN_MAX_DEPTH && cap >= 0 && n0 >= 0 && n0 <= cap && counts_dev && ckeys &&
+                 cvals && parent && coarse_coords);
+  SGNN_CHECK_ARG(ccap >= 2 * cap && ccap >= 2 && (ccap & (ccap - 1)) == 0 && ccap < (1ll << 31));
+  for (int l = 0; l < depth; ++l) SGNN_CHECK_ARG(ckeys[l] && (cap == 0 || (cvals[l] && parent[l] && coarse_coords[l])));
+  SGNN_CHECK_ARG(cap == 0 || fine_coords);
+  return down2_chain("sgnn_down2_chain", fine_coords, n0, n0_dev, cap, depth, ckeys, cvals, ccap, parent, coarse_coords,
+                     counts_dev, level_caps, status, ws, ws_bytes, (hipStream_t)stream);
+}
+
+// Capacity mode: the pyramid and its children / ptable tables in one submission.  Every level has a scratch slice of its
+// own, so one launch initialises them all and the insertion of level l + 1 can share a launch with the tables pass of
+// level l: 3 launches per level + 2 (init; insert of level 0; per level count, write, parent + tables [+ insert]).
+// sgnn_tune.scan_inline = 0 adds the scan launch, chain_merged = 0 a separate insert per inner level: 5 per level + 1.
+// Same first-touch order, same tables as sgnn_down2_chain + sgnn_down2_tables (tests/test_gpu_capacity.py).
+// level l: children[l] is (8 x ldc[l]) with ldc[l] = roundup256(level_caps[l]), ptable[l] is (8 x ldf[l]) with
+// ldf[0] = roundup256(cap), ldf[l] = ldc[l-1].  All pointer arrays are HOST arrays.
 SGNN_EXPORT int sgnn_down2_chain_tables(const int32_t *fine_coords, const int64_t *n0_dev, int64_t cap, int depth,
                                         void *const *ckeys, void *const *cvals, int64_t ccap, void *const *parent,
                                         void *const *coarse_coords, int64_t *counts_dev, const int64_t *level_caps,
@@ -1240,54 +1179,42 @@ SGNN_EXPORT int sgnn_down2_chain_tables(const int32_t *fine_coords, const int64_
   SGNN_CHECK_ARG(depth >= 1 && depth <= CHAIN_MAX_DEPTH && cap >= 1 && n0_dev && counts_dev && level_caps && status &&
                  ckeys && cvals && parent && coarse_coords && children && ptable && fine_coords);
   SGNN_CHECK_ARG(ccap >= 2 * cap && ccap >= 2 && (ccap & (ccap - 1)) == 0 && ccap < (1ll << 31));
-  if (!ws || ws_bytes < sgnn_down2_chain_tables_ws_bytes(cap, depth)) {
+  if (!ws || ws_bytes < chain_ws_bytes(cap, ccap, depth)) {
     sgnn_set_error("sgnn_down2_chain_tables: workspace too small");
     return SGNN_ENOWS;
   }
-  const int64_t nblk = (cap + SCAN_BLOCK - 1) / SCAN_BLOCK;
-  int32_t *base = (int32_t *)ws;
-  int32_t *slot_of[CHAIN_MAX_DEPTH], *rank_at[CHAIN_MAX_DEPTH], *owner[CHAIN_MAX_DEPTH];
+  ChainScratch w[CHAIN_MAX_DEPTH];
+  int32_t *block_sums = chain_ws_carve(ws, cap, ccap, depth, w);
   ChainInit ini{};
   for (int l = 0; l < depth; ++l) {
     SGNN_CHECK_ARG(ckeys[l] && cvals[l] && parent[l] && coarse_coords[l] && children[l] && ptable[l] && level_caps[l] >= 1);
-    slot_of[l] = base;
-    rank_at[l] = base + cap;
-    owner[l] = base + 2 * cap;
-    base += 2 * cap + ccap;
     ini.ckeys[l] = (unsigned long long *)ckeys[l];
-    ini.owner[l] = owner[l];
-    ini.rank_at[l] = rank_at[l];
+    ini.owner[l] = w[l].owner;
+    ini.rank_at[l] = w[l].rank_at;
   }
-  int32_t *block_sums = base;
   ini.ccap = ccap;
   ini.cap = cap;
-  ini.depth = depth;
-  const int64_t top = ccap > cap ? ccap : cap;
-  SGNN_LAUNCH(k_chain_init_all, dim3(sgnn_grid_for(top * depth, 256, 8192)), dim3(256), 0, s, ini);
+  chain_launch_init(ini, depth, s);
   const int4 *fine = (const int4 *)fine_coords;
   const int64_t *n_dev = n0_dev;
   int64_t fine_cap = cap;
   const int g = sgnn_grid_for(cap, 256, 8192);
-  const bool inl = scan_inline_ok(nblk), merged = g_tune.chain_merged != 0;
+  const bool merged = g_tune.chain_merged != 0;
   for (int l = 0; l < depth; ++l) {
     const int64_t ccap_l = level_caps[l] < cap ? level_caps[l] : cap;
     const int64_t ldc = ((ccap_l + 255) / 256) * 256, ldf = ((fine_cap + 255) / 256) * 256;
     if (l == 0 || !merged)     // (merged: level l's insertion ran in the tables launch of level l - 1)
-      SGNN_LAUNCH(k_chain_insert, dim3(g), dim3(256), 0, s, fine, n_dev, cap, (unsigned long long *)ckeys[l], owner[l],
-                         (uint64_t)(ccap - 1), slot_of[l]);
-    SGNN_LAUNCH(k_chain_count, dim3((unsigned)nblk), dim3(256), 0, s, (const int32_t *)slot_of[l],
-                       (const int32_t *)owner[l], n_dev, cap, block_sums);
-    const ScanLimit lim{ccap_l, nullptr, 0, status};
-    if (!inl) SGNN_LAUNCH(k_scan_block_sums, dim3(1), dim3(1024), 0, s, block_sums, nblk, counts_dev + l, lim);
-    SGNN_LAUNCH(k_chain_emit2, dim3((unsigned)nblk), dim3(256), 0, s, fine, (const int32_t *)slot_of[l],
-                       (const int32_t *)owner[l], n_dev, cap, (const int32_t *)block_sums, (int4 *)coarse_coords[l],
-                       rank_at[l], (const int64_t *)(counts_dev + l), (int32_t *)children[l], ldc,
-                       inl ? ScanInline{nblk, counts_dev + l, lim} : kNoInline);
-    const ChainTables t{fine, n_dev, cap, owner[l], rank_at[l], slot_of[l], (int32_t *)parent[l], (int32_t *)cvals[l],
+      chain_launch_insert(fine, n_dev, cap, cap, ckeys[l], w[l], ccap, s);
+    const ScanInline si = chain_launch_count(w[l], n_dev, cap, cap, block_sums, counts_dev + l,
+                                             ScanLimit{ccap_l, nullptr, 0, status}, s);
+    SGNN_LAUNCH(k_chain_emit2, dim3((unsigned)((cap + SCAN_BLOCK - 1) / SCAN_BLOCK)), dim3(256), 0, s, fine,
+                (const int32_t *)w[l].slot_of, (const int32_t *)w[l].owner, n_dev, cap, (const int32_t *)block_sums,
+                (int4 *)coarse_coords[l], w[l].rank_at, (const int64_t *)(counts_dev + l), (int32_t *)children[l], ldc, si);
+    const ChainTables t{fine, n_dev, cap, w[l].owner, w[l].rank_at, w[l].slot_of, (int32_t *)parent[l], (int32_t *)cvals[l],
                         counts_dev + l, ccap_l, (int32_t *)children[l], ldc, (int32_t *)ptable[l], ldf};
     if (merged && l + 1 < depth)
-      SGNN_LAUNCH(k_chain_tables_insert, dim3(g), dim3(256), 0, s, t, (unsigned long long *)ckeys[l + 1], owner[l + 1],
-                         (uint64_t)(ccap - 1), slot_of[l + 1], (const int4 *)coarse_coords[l], cap);
+      SGNN_LAUNCH(k_chain_tables_insert, dim3(g), dim3(256), 0, s, t, (unsigned long long *)ckeys[l + 1], w[l + 1].owner,
+                  (uint64_t)(ccap - 1), w[l + 1].slot_of, (const int4 *)coarse_coords[l], cap);
     else
       SGNN_LAUNCH(k_chain_parent_tables, dim3(g), dim3(256), 0, s, t);
     fine = (const int4 *)coarse_coords[l];
@@ -1298,6 +1225,7 @@ SGNN_EXPORT int sgnn_down2_chain_tables(const int32_t *fine_coords, const int64_
   return SGNN_OK;
 }
 
+// tables of one level from its parent[] (the step-by-step form: the host knows both row counts, or their bounds)
 __global__ __launch_bounds__(256) void k_down2_tables(const int4 *__restrict__ fine,
                                                      const int32_t *__restrict__ parent, int64_t nf,
                                                      int32_t *__restrict__ children, int64_t ldc,
@@ -1309,18 +1237,10 @@ __global__ __launch_bounds__(256) void k_down2_tables(const int4 *__restrict__ f
   const int64_t stride = (int64_t)gridDim.x * 256;
   const int64_t iend = pad_end(nf, ldf);
   for (; i < iend; i += stride) {
-    if (i >= nf) {  // padding
-#pragma unroll
-      for (int k = 0; k < 8; ++k) ptable[(int64_t)k * ldf + i] = -1;
-      continue;
-    }
-    const int4 c = fine[i];
-    const int off = ((c.x & 1) << 2) | ((c.y & 1) << 1) | (c.z & 1);
-    int32_t p = parent[i];
-    if (p >= nc) p = -1;       // only after a capacity overflow (the step is flagged and discarded): stay in bounds
-    if (p >= 0) children[(int64_t)off * ldc + p] = (int32_t)i;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) ptable[(int64_t)k * ldf + i] = (k == off) ? p : -1;
+    if (i >= nf)
+      down2_table_row<false>(i, true, fine, -1, nc, nullptr, children, ldc, ptable, ldf);
+    else
+      down2_table_row<false>(i, false, fine, parent[i], nc, nullptr, children, ldc, ptable, ldf);
   }
 }
 

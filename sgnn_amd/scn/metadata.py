@@ -280,13 +280,7 @@ def build_down2(fine):
     _lib.call('sgnn_rulebook_down2', ptr(fine.coords), nf, ptr(ckeys), ptr(cvals), ccap, ptr(parent), ptr(ccoords),
               ptr(rt.state), ptr(ws), wsb)
     nc = rt.read_count()  # host sync: the coarse row count sizes every downstream buffer
-    coarse = Grid(ccoords[:nc], ckeys, cvals, ccap)
-    ldc, ldf = coarse.ld, fine.ld
-    children = torch.empty(8 * ldc, dtype=torch.int32, device=dev)
-    ptable = torch.empty(8 * ldf, dtype=torch.int32, device=dev)  # rows >= nf are never read
-    _lib.call('sgnn_down2_tables', ptr(fine.coords), ptr(parent), nf, ptr(children), ldc, nc, ptr(ptable), ldf, None,
-              None)
-    return Down2(fine, coarse, parent[:nf], children, ldc, ptable, ldf)
+    return _down2_tables(fine, Grid(ccoords[:nc], ckeys, cvals, ccap), parent)
 
 
 CHAIN = True    # False: one stride-2 build + one host read-back per level (the round-1 behaviour)

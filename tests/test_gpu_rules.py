@@ -357,3 +357,33 @@ def test_down2_chain_tables_overflow(order, n, depth, at, scan_inline, chain_mer
     for preset in (0, R.STATUS_DUPLICATE):
         what = 'down2_chain_tables %s n=%d depth=%d overflow at %s level_caps=%s' % (order, n, depth, at, caps)
         assert _chain(c, depth, caps, True, True, preset, what) == (at is not None)
+
+
+def test_down2_launch_counts(scan_inline, chain_merged, monkeypatch):
+    """Kernel launches of the three stride-2 builders (sgnn_launch_count around each call), 300 sites at depth 2:
+    sgnn_rulebook_down2 5 and sgnn_down2_chain 5 per level, one more each for the scan launch of scan_inline = 0;
+    sgnn_down2_chain_tables 3 per level + 2 at the defaults, 5 per level + 1 with both switches off."""
+    lib, launches = L(), {}
+    real_call = lib.call
+
+    def counting_call(name, *args):
+        before = lib.query('sgnn_launch_count')
+        real_call(name, *args)
+        launches[name] = lib.query('sgnn_launch_count') - before
+
+    monkeypatch.setattr(lib, 'call', counting_call)
+    c, depth = R.cloud('shuffled', 300), 2
+    caps = [R.chain_cap(len(c))] * depth
+    _down2(c, 'launch counts: down2')
+    _chain(c, depth, None, True, False, 0, 'launch counts: chain')
+    _chain(c, depth, caps, True, True, 0, 'launch counts: chain_tables')
+    scan = 0 if scan_inline else 1
+    assert launches['sgnn_rulebook_down2'] == 5 + scan
+    assert launches['sgnn_down2_chain'] == (5 + scan) * depth
+    # one init, per level count (+ scan) + write + tables, and the insertions: one launch of their own for level 0 only
+    # (chain_merged: the others ride in the tables launch of the level above) or for every level
+    assert launches['sgnn_down2_chain_tables'] == 1 + (3 + scan) * depth + (1 if chain_merged else depth)
+    if scan_inline and chain_merged:
+        assert launches['sgnn_down2_chain_tables'] == 3 * depth + 2
+    if not scan_inline and not chain_merged:
+        assert launches['sgnn_down2_chain_tables'] == 5 * depth + 1

@@ -108,7 +108,10 @@ typedef struct sgnn_tune {
    * workgroups to be resident at once (no partial second round); 0 = one tile per workgroup.  Rows bit-identical; BatchNorm
    * statistics partials are summed per workgroup, so their fp64 grouping differs.  The tile count follows the workgroups of
    * the kernel the DEVICE holds at once (occupancy x compute units, queried per device on first use): statistics are
-   * bit-reproducible for a given device model, driver and compiler, not across them.  Default 1. */
+   * bit-reproducible for a given device model, driver and compiler, not across them — nor across library versions that
+   * change a kernel's occupancy (the wide-row 26 / 30-channel straight-line kernels hold two workgroups per CU since their
+   * weights stay resident in LDS, one before: their tile count per workgroup halved, their partials group differently).
+   * Default 1. */
   int64_t conv_one_round;
   /* epilogue of the 256-row walk for output rows of 8 / 12 / 16 channels (torch/model.py:38-42, 180, 255, forward and data
    * gradient): 1 = the tile leaves the MFMA layout through a quad transpose, so the residual addend, the BatchNorm input of

@@ -21,6 +21,26 @@ struct ConvCfg {
 #endif
   static constexpr int KC_RAW = CONV_LDS_FLOATS / PER_K;
   static constexpr int KC = KC_RAW < 1 ? 1 : (KC_RAW > 27 ? 27 : KC_RAW);
+  // The straight-line kernels (conv_unrolled.hip) keep ALL 27 slices of a 3x3x3 filter resident when the image and the
+  // fp64 statistics scratch (4 waves x 2 sums x NT*16 doubles) fit in CONV_RESIDENT_LDS_BYTES per workgroup: the tile is
+  // then staged once per workgroup instead of 27 / KC times per 256-row tile.  A gfx950 CU has 160 KiB of LDS.  The
+  // wide-row shapes up to <34,16> need at most 62 KiB: two workgroups per CU, which is also what their registers allow
+  // (chunked, with barriers inside the offset sequence, they needed 410-512 registers: ONE workgroup per CU).  <16,34>
+  // needs 84 KiB: one workgroup per CU, as before (490 registers chunked).  No resident-workgroup count drops; where it
+  // rises, the J-tile decomposition of a level follows (conv_wg_capacity).  profiles/conv_wide_resident.json has the table.
+  // Other targets (64 KiB of LDS per CU and per workgroup) keep the 32 KiB chunks.
+  // 96 KiB = the most ONE workgroup may take where its registers allow only one per CU anyway (of 160 KiB); a shape that
+  // holds two workgroups per CU must stay within 160 KiB / 2 = 80 KiB (all of them are <= 62 KiB) — conv_unrolled.hip
+  // asserts it, so that a new shape cannot take more and silently lose its second workgroup.
+#ifndef CONV_RESIDENT_LDS_BYTES
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
+#define CONV_RESIDENT_LDS_BYTES 0
+#else
+#define CONV_RESIDENT_LDS_BYTES 98304
+#endif
+#endif
+  static constexpr int RESIDENT_BYTES = 27 * PER_K * 4 + 4 * 2 * NT * 16 * 8;   // image + statistics scratch
+  static constexpr int KC27 = (RESIDENT_BYTES <= CONV_RESIDENT_LDS_BYTES) ? 27 : KC;
   // widest load that is aligned for every (row, q)
   static constexpr int ALIGN = ((CIN % 4 == 0) && (V % 4 == 0)) ? 16 : (((CIN % 2 == 0) && (V % 2 == 0)) ? 8 : 4);
 };
@@ -48,6 +68,9 @@ struct ConvEx {
 // A failed query is NOT cached (0 = "one-round mode off" would otherwise stick for the life of the process).  The J-tile
 // decomposition of a level — and with it the fp64 grouping of the BatchNorm statistics partials — follows this value, so
 // statistics are bit-reproducible per (device model, driver, compiler), not across them (include/sgnn_hip.h says so).
+// Nor across versions of this library that change a kernel's occupancy: with the resident weight image (ConvCfg::KC27) the
+// 26 / 30-channel k_conv_fwd_u shapes hold two workgroups per CU where the chunked form held one, so their J halved and
+// their partials group differently than before (rows are unchanged; profiles/conv_wide_resident.json).
 // hipOccupancyMaxActiveBlocksPerMultiprocessor is a host-side query: legal during a stream capture.
 template <auto KERNEL>
 static int conv_wg_capacity() {

@@ -13,8 +13,10 @@
 //  * tail handling (clamped offsets, dropped gathers) costs loads that are thrown away.
 // Straight-line code has no merge points: every wait is a counted vmcnt(n) that covers exactly the register set about to
 // be used.  The wave's K rule entries are loaded up front (K VGPRs, one coalesced 256-byte load each), the rows of offset
-// k + 1 are gathered while the MFMAs of offset k run.  Weights are staged KC offsets at a time (<= 32 KiB of LDS) between
-// two barriers at compile-time positions of the unrolled sequence; ordinary loads in flight survive a barrier.
+// k + 1 are gathered while the MFMAs of offset k run.  The whole filter is staged into LDS once per workgroup, in front of
+// its first row tile, where the target has the LDS for it (ConvCfg::KC27; gfx950: 48-84 KiB): no barrier inside the offset
+// sequence, and the J row tiles of a workgroup share one weight image.  Elsewhere it is staged KC offsets at a time (<= 32 KiB)
+// between two barriers at compile-time positions of the unrolled sequence; ordinary loads in flight survive a barrier.
 #include "conv_common.h"
 
 // WEPI: the wide (row-contiguous, 16-byte) epilogue of conv_common.h (output rows of 8 / 12 / 16 channels)
@@ -25,7 +27,9 @@ __device__ __forceinline__ void conv_fwd_u_body(const float *__restrict__ x, int
                                                 int flags, int in_shift, const ConvEpi &epi, int wg_cap) {
   using C = ConvCfg<CIN, COUT>;
   constexpr int V = C::V, CINP = C::CINP, NT = C::NT, M = 4;
-  constexpr int KC = C::KC < K ? C::KC : K;            // offsets per staged weight chunk
+  constexpr int KC = C::KC27 < K ? C::KC27 : K;        // offsets per staged weight chunk (K when the whole filter is resident)
+  // more than half a CU's LDS makes a kernel one-workgroup-per-CU: only <16,34> may, its registers allow one anyway (conv_common.h)
+  static_assert(KC < 27 || C::RESIDENT_BYTES <= 80 * 1024 || (CIN == 16 && COUT == 34), "resident weight image costs a workgroup per CU");
   __shared__ __attribute__((aligned(16))) float wl[KC * C::PER_K];
   __shared__ double sred[4 * 2 * NT * 16];             // statistics scratch (the weight tile stays live across row tiles)
   static_assert(!WEPI || (NT == 1 && COUT % 4 == 0), "wide epilogue: one column tile of whole 16-byte chunks");
@@ -150,7 +154,7 @@ __global__ __launch_bounds__(256) void k_conv_fwd_u(const float *__restrict__ x,
 
 // the stride-2 (8-offset) walks with the wide epilogue: with 32 gathers per 64-row tile the element-wise epilogue's 16-48
 // memory instructions weigh more than anywhere else.  Occupancy pinned like k_conv_fwd_w (conv.hip explains).  The 27-offset
-// wide-row shapes keep the element-wise form: their walk already needs 190-240 registers.
+// wide-row shapes keep the element-wise form: their walk already needs 168-291 registers (two workgroups per CU at most).
 template <int CIN, int COUT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_conv_fwd_uw(
     const float *__restrict__ x, int64_t n_in, const float *__restrict__ w, const int32_t *__restrict__ table, int64_t ld,

@@ -912,6 +912,44 @@ int sgnn_cc_face_labels(const int32_t *faces, int ntri, int nverts, const int32_
                         int32_t *face_labels, int64_t *face_sizes, sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Mesh simplification by vertex clustering with quadric placement (sgnn_amd.simplify; rules in INTEGRATION.md
+ * section K).  The caller chains the stages and reads the counts back in between:
+ *   sgnn_simp_keys     -> keys[i] = (cx << 42) | (cy << 21) | cz with c = floor((v - origin) / cell) in fp32 per axis;
+ *                         origin: 3 floats on the device.  A non-finite coordinate or a cell index outside [0, 2^21)
+ *                         gives the key -1 and raises SGNN_STATUS_COORD_RANGE in *status; such a vertex joins no cluster.
+ *   sgnn_simp_clusters -> first_of[i] = smallest vertex index with vertex i's key (-1 for the key -1), is_first[i] u8;
+ *                         tkeys (cap) i64 and tfirst (cap) i32 are the hash table, initialised here,
+ *                         cap >= sgnn_weld_slots(nv)
+ *   (caller: sel = sgnn_compact_mask(is_first), nclust = its count; rank = sgnn_weld_number(sel): cluster k is the
+ *    one with the k-th smallest first member)
+ *   sgnn_simp_corners  -> corner_first[3t + k] = first_of[faces[t][k]].  A face with an index outside [0, nverts) is
+ *                         not dereferenced and raises SGNN_STATUS_COORD_RANGE in *status; it, and a face on a vertex
+ *                         without a key, get vertex 0 three times: in range, and degenerate to every later stage.
+ *   (caller: sgnn_mesh_faces(corner_first, rank) remaps the faces to cluster numbers and flags the ones that stay;
+ *    sgnn_compact_mask + sgnn_take_rows3 -> kept faces)
+ *   sgnn_simp_mark     -> used[c] = 1 (u8, zeroed by the caller) for every cluster c in [0, nclust) of cfaces (nfaces,3)
+ *   (caller: csel = sgnn_compact_mask(used): output vertex p is cluster csel[p]; order = corner numbers sorted stably
+ *    by cluster, start (nclust + 1) = where each cluster's corners begin in order)
+ *   sgnn_simp_place    -> out_verts (nout,3) f32 and, with colors, out_colors (nout,3) u8 of the clusters csel[p]:
+ *                         one lane per cluster sums its corners order[start[c] .. start[c+1]) in that order in fp64 and
+ *                         solves for the vertex.  quadric = 1: section K's regularised quadric minimiser, 0: the mean.
+ *                         sel[c] = first member of cluster c; keys as above.  A corner whose face has a bad index is
+ *                         passed over.
+ * No floating-point atomics anywhere: the same input gives the same bits.  nverts < 2^31, 3 * ntri < 2^31.
+ * ------------------------------------------------------------------------- */
+int sgnn_simp_keys(const float *verts, int64_t nv, const float *origin, float cell, int64_t *keys, int32_t *status,
+                   sgnn_stream_t stream);
+int sgnn_simp_clusters(const int64_t *keys, int64_t nv, int64_t *tkeys, int32_t *tfirst, int64_t cap,
+                       int32_t *first_of, uint8_t *is_first, sgnn_stream_t stream);
+int sgnn_simp_corners(const int32_t *faces, int ntri, int nverts, const int32_t *first_of, int32_t *corner_first,
+                      int32_t *status, sgnn_stream_t stream);
+int sgnn_simp_mark(const int32_t *cfaces, int64_t nfaces, int64_t nclust, uint8_t *used, sgnn_stream_t stream);
+int sgnn_simp_place(const float *verts, int nverts, const int32_t *faces, int ntri, const uint8_t *colors,
+                    const int64_t *order, const int64_t *start, const int32_t *csel, int64_t nout, const int32_t *sel,
+                    const int64_t *keys, const float *origin, float cell, int quadric, float *out_verts,
+                    uint8_t *out_colors, sgnn_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Evaluation metrics on the device.
  * ------------------------------------------------------------------------- */
 /* IoU ingredients of one hierarchy level (torch/loss.py:84-120 compute_iou_sparse_dense, fed as in

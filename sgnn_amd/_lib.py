@@ -161,6 +161,12 @@ PROTOTYPES = {
     'sgnn_cc_flatten': (c_i32, [c_vp, c_i64, c_vp, c_vp]),
     'sgnn_cc_relabel': (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),
     'sgnn_cc_face_labels': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    'sgnn_simp_keys': (c_i32, [c_vp, c_i64, c_vp, c_f32, c_vp, c_vp, c_vp]),
+    'sgnn_simp_clusters': (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    'sgnn_simp_corners': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    'sgnn_simp_mark': (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp]),
+    'sgnn_simp_place': (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_i32,
+                                c_vp, c_vp, c_vp]),
     'sgnn_iou_counts': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'sgnn_l1_tgtsurf_ws_bytes': (c_i64, []),
     'sgnn_l1_tgtsurf': (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp, c_i64, c_vp]),

@@ -989,8 +989,6 @@ int sgnn_mc_count(const float *tsdf, int d0, int d1, int d2, float isovalue, flo
 int sgnn_mc_emit(const float *tsdf, const uint8_t *colors, int d0, int d1, int d2, float isovalue,
                  float truncation, float thresh, void *ws, int64_t ws_bytes, float *verts, uint8_t *vcols,
                  sgnn_stream_t stream);
-/* hash slots needed for n keys (vertices for the weld, triangles for the duplicate-face set) */
-int64_t sgnn_weld_slots(int64_t n);
 /* cells (nv,3) i32 = grid cell of every vertex at pitch `thresh` (the reference passes 1e-5);
  * rep/first (cap) i32, state (cap) u8: the cell table, initialised here */
 int sgnn_weld_build(const float *verts, int64_t nv, float thresh, int32_t *cells, int32_t *rep, int32_t *first,
@@ -1001,6 +999,11 @@ int sgnn_weld_sweep(const int32_t *cells, const int32_t *rep, const int32_t *fir
 int sgnn_weld_lookup(const int32_t *cells, int64_t nv, const int32_t *rep, const int32_t *first,
                      const uint8_t *state, int64_t cap, int32_t *creator_of, uint8_t *is_creator,
                      sgnn_stream_t stream);
+
+/* Shared mesh tables (csrc/mesh_tables.hip): what marching cubes' clean-up, sgnn_amd.components and sgnn_amd.simplify
+ * have in common. */
+/* hash slots needed for n keys (vertices for the weld and the clusters, triangles for the duplicate-face set) */
+int64_t sgnn_weld_slots(int64_t n);
 /* newid[sel[p]] = p */
 int sgnn_weld_number(const int32_t *sel, int64_t n, int32_t *newid, sgnn_stream_t stream);
 int sgnn_mesh_faces(const int32_t *creator_of, const int32_t *newid, int64_t ntri, int32_t *faces, int32_t *frep,

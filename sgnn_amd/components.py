@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .marching_cubes import _compact
+from ._glue import compact, number, take3
 
 TILE_ZYX = (8, 8, 32)       # SGNN_CC_TILE_Z, _Y, _X of include/sgnn_hip.h: the tile that one workgroup labels in LDS
 STATUS_INDEX_RANGE = 1      # SGNN_STATUS_COORD_RANGE
@@ -49,10 +49,8 @@ def _number(parent, n, dev):
         return torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int64, device=dev)
     is_root = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
     _lib.call('sgnn_cc_flatten', _lib.ptr(parent), n, _lib.ptr(is_root))
-    sel, ncomp = _compact(is_root, n, dev)                     # stable: sel[k] = k-th smallest root
-    rank = torch.empty(max(n, 1), dtype=torch.int32, device=dev)      # read at roots only
-    if ncomp:
-        _lib.call('sgnn_weld_number', _lib.ptr(sel), ncomp, _lib.ptr(rank))
+    sel, ncomp = compact(is_root, n, dev)                      # stable: sel[k] = k-th smallest root
+    rank = number(sel, ncomp, n, dev)                          # read at roots only
     labels = torch.empty(n, dtype=torch.int32, device=dev)
     sizes = torch.zeros(max(ncomp, 1), dtype=torch.int64, device=dev)
     _lib.call('sgnn_cc_relabel', _lib.ptr(parent), n, _lib.ptr(rank), ncomp, _lib.ptr(labels), _lib.ptr(sizes))
@@ -228,13 +226,6 @@ def filter_sparse(locs, vals, dims_zyx, min_size=None, keep_largest=None, connec
     return locs[rows], vals[rows], rows
 
 
-def _take3(src, elem_bytes, sel, n, dtype):
-    out = torch.empty((n, 3), dtype=dtype, device=src.device)
-    if n:
-        _lib.call('sgnn_take_rows3', _lib.ptr(src), elem_bytes, _lib.ptr(sel), n, _lib.ptr(out))
-    return out
-
-
 def filter_mesh(verts, faces, colors=None, min_size=None, keep_largest=None):
     """(verts, faces) or, with colors, (verts, faces, colors) of the kept components of a welded mesh; sizes are face
     counts.  Kept faces stay in order; vertices that no kept face uses are removed and the others keep their order;
@@ -251,12 +242,10 @@ def filter_mesh(verts, faces, colors=None, min_size=None, keep_largest=None):
     faces, nv, nt = _faces(verts, faces)
     dev = faces.device
     keep = select(lab.face_sizes, min_size, keep_largest)
-    vsel, n_new = _compact(_kept(lab.vertex_labels, keep).to(torch.uint8), nv, dev)
-    fsel, n_faces = _compact(_kept(lab.face_labels, keep).to(torch.uint8), nt, dev)
-    newid = torch.empty(max(nv, 1), dtype=torch.int32, device=dev)
-    if n_new:
-        _lib.call('sgnn_weld_number', _lib.ptr(vsel), n_new, _lib.ptr(newid))
-    out_f = _take3(faces, 4, fsel, n_faces, torch.int32)
+    vsel, n_new = compact(_kept(lab.vertex_labels, keep).to(torch.uint8), nv, dev)
+    fsel, n_faces = compact(_kept(lab.face_labels, keep).to(torch.uint8), nt, dev)
+    newid = number(vsel, n_new, nv, dev)                       # read at kept vertices only
+    out_f = take3(faces, 4, fsel, n_faces, torch.int32)
     out_f = newid[out_f.long()] if n_faces else out_f
-    out = (_take3(verts.contiguous(), 4, vsel, n_new, torch.float32), out_f)
-    return out if colors is None else out + (_take3(colors.contiguous(), 1, vsel, n_new, torch.uint8),)
+    out = (take3(verts.contiguous(), 4, vsel, n_new, torch.float32), out_f)
+    return out if colors is None else out + (take3(colors.contiguous(), 1, vsel, n_new, torch.uint8),)

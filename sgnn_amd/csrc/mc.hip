@@ -20,6 +20,7 @@
 // All passes are HBM/latency-bound streaming or hash-probe passes; nothing here is GEMM-shaped.
 #include <mutex>
 #include "common.h"
+#include "first_table.h"
 #include "mc_table.h"
 
 #define MC_BLOCK 256
@@ -320,21 +321,8 @@ SGNN_EXPORT int sgnn_mc_emit(const float *tsdf, const uint8_t *colors, int d0, i
 // ---------------------------------------------------------------------------------------------------------
 // welding (merge_close_vertices with approx = true, :398-415)
 // ---------------------------------------------------------------------------------------------------------
-#define WELD_EMPTY (-1)
 enum { W_UNDECIDED = 0, W_IN = 1, W_OUT = 2 };
-
-struct Cell {
-  int x, y, z;
-};
-__device__ __forceinline__ bool operator==(const Cell &a, const Cell &b) { return a.x == b.x && a.y == b.y && a.z == b.z; }
-
-__device__ __forceinline__ uint64_t weld_hash(const Cell &c) {
-  uint64_t h = (uint64_t)(uint32_t)c.x * 0x9E3779B97F4A7C15ull;
-  h ^= (uint64_t)(uint32_t)c.y * 0xC2B2AE3D27D4EB4Full + (h << 6) + (h >> 2);
-  h ^= (uint64_t)(uint32_t)c.z * 0x165667B19E3779F9ull + (h << 6) + (h >> 2);
-  h ^= h >> 29;
-  return h;
-}
+using Cell = Key3;      // a vertex's grid cell at pitch thresh
 
 __device__ __forceinline__ int weld_sgn(float v) { return (0.0f < v) - (v < 0.0f); }
 
@@ -351,38 +339,21 @@ __global__ __launch_bounds__(256) void k_weld_cells(const float *__restrict__ ve
   cells[i] = c;
 }
 
-// open addressing keyed by the cell, but a slot stores a VERTEX: rep[slot] = some vertex of the cell (claimed by
-// CAS; its cell, written by the previous kernel, is the slot's key), first[slot] = smallest vertex index of the cell
+// the cell table (first_table.h): rep[slot] = some vertex of the cell, whose cell, written by the previous kernel, is the
+// slot's key; first[slot] = smallest vertex index of the cell
 __global__ __launch_bounds__(256) void k_weld_insert(const Cell *__restrict__ cells, int64_t nv,
                                                     int32_t *__restrict__ rep, int32_t *__restrict__ first,
                                                     int64_t cap) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= nv) return;
   const Cell c = cells[i];
-  int64_t h = (int64_t)(weld_hash(c) % (uint64_t)cap);
-  for (;;) {
-    int32_t cur = __hip_atomic_load(&rep[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == WELD_EMPTY) {
-      const int32_t old = atomicCAS(&rep[h], WELD_EMPTY, (int32_t)i);
-      cur = old == WELD_EMPTY ? (int32_t)i : old;
-    }
-    if (cells[cur] == c) {
-      atomicMin(&first[h], (int32_t)i);
-      return;
-    }
-    h = h + 1 == cap ? 0 : h + 1;
-  }
+  first_insert(rep, first, cap, (int64_t)(weld_hash(c) % (uint64_t)cap), (int32_t)i, (int32_t)i,
+               [&](int32_t v) { return cells[v] == c; });
 }
 
 __device__ __forceinline__ int64_t weld_find(const Cell &c, const Cell *__restrict__ cells,
                                              const int32_t *__restrict__ rep, int64_t cap) {
-  int64_t h = (int64_t)(weld_hash(c) % (uint64_t)cap);
-  for (;;) {
-    const int32_t cur = rep[h];
-    if (cur == WELD_EMPTY) return -1;
-    if (cells[cur] == c) return h;
-    h = h + 1 == cap ? 0 : h + 1;
-  }
+  return first_find(rep, cap, (int64_t)(weld_hash(c) % (uint64_t)cap), [&](int32_t v) { return cells[v] == c; });
 }
 
 // one sweep of the greedy independent-set fixed point over the occupied slots
@@ -390,7 +361,7 @@ __global__ __launch_bounds__(256) void k_weld_sweep(const Cell *__restrict__ cel
                                                    const int32_t *__restrict__ first, uint8_t *state, int64_t cap,
                                                    unsigned long long *__restrict__ undecided) {
   const int64_t h = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (h >= cap || rep[h] == WELD_EMPTY) return;
+  if (h >= cap || rep[h] == SLOT_EMPTY<int32_t>) return;
   if (__hip_atomic_load(&state[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != W_UNDECIDED) return;
   const Cell c = cells[rep[h]];
   const int32_t f = first[h];
@@ -437,8 +408,6 @@ __global__ __launch_bounds__(256) void k_weld_lookup(const Cell *__restrict__ ce
   is_creator[i] = creator;
 }
 
-SGNN_EXPORT int64_t sgnn_weld_slots(int64_t n) { return n < 8 ? 16 : 2 * n + 1; }
-
 SGNN_EXPORT int sgnn_weld_build(const float *verts, int64_t nv, float thresh, int32_t *cells, int32_t *rep,
                                 int32_t *first, uint8_t *state, int64_t cap, sgnn_stream_t stream) {
   SGNN_CHECK_ARG(nv >= 0 && nv < ((int64_t)1 << 31) && thresh > 0.f && cap >= sgnn_weld_slots(nv) && rep && first && state);
@@ -474,128 +443,6 @@ SGNN_EXPORT int sgnn_weld_lookup(const int32_t *cells, int64_t nv, const int32_t
   SGNN_CHECK_ARG(cells && rep && first && state && creator_of && is_creator);
   SGNN_LAUNCH(k_weld_lookup, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const Cell *)cells, nv, rep, first, state, cap, creator_of, is_creator);
-  SGNN_CHECK_LAUNCH();
-  return SGNN_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// faces: remap through the weld, drop degenerate (:298-321) and duplicate (:266-297) triangles
-// ---------------------------------------------------------------------------------------------------------
-struct Tri {
-  int a, b, c;
-};
-__device__ __forceinline__ Tri tri_sorted(const int32_t *__restrict__ f) {
-  int a = f[0], b = f[1], c = f[2], t;
-  if (a > b) { t = a; a = b; b = t; }
-  if (b > c) { t = b; b = c; c = t; }
-  if (a > b) { t = a; a = b; b = t; }
-  return Tri{a, b, c};
-}
-
-// newid[sel[p]] = p : new index of every creator vertex (cnt order of :405-410 = soup order)
-__global__ __launch_bounds__(256) void k_weld_number(const int32_t *__restrict__ sel, int64_t n, int32_t *__restrict__ newid) {
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p < n) newid[sel[p]] = (int32_t)p;
-}
-
-__global__ __launch_bounds__(256) void k_faces_remap(const int32_t *__restrict__ creator_of,
-                                                    const int32_t *__restrict__ newid, int64_t ntri,
-                                                    int32_t *__restrict__ faces) {
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e < 3 * ntri) faces[e] = newid[creator_of[e]];
-}
-
-__device__ __forceinline__ bool tri_degenerate(const int32_t *__restrict__ f) {
-  return f[0] == f[1] || f[0] == f[2] || f[1] == f[2];
-}
-__device__ __forceinline__ bool tri_same(const Tri &a, const Tri &b) { return a.a == b.a && a.b == b.b && a.c == b.c; }
-
-// set of unordered vertex triples, same slot-stores-an-index scheme; degenerate faces never enter it (:440 runs first)
-__global__ __launch_bounds__(256) void k_faces_insert(const int32_t *__restrict__ faces, int64_t ntri,
-                                                     int32_t *__restrict__ frep, int32_t *__restrict__ ffirst,
-                                                     int64_t cap) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= ntri || tri_degenerate(faces + 3 * t)) return;
-  const Tri key = tri_sorted(faces + 3 * t);
-  int64_t h = (int64_t)(weld_hash(Cell{key.a, key.b, key.c}) % (uint64_t)cap);
-  for (;;) {
-    int32_t cur = __hip_atomic_load(&frep[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == WELD_EMPTY) {
-      const int32_t old = atomicCAS(&frep[h], WELD_EMPTY, (int32_t)t);
-      cur = old == WELD_EMPTY ? (int32_t)t : old;
-    }
-    if (tri_same(tri_sorted(faces + 3 * (int64_t)cur), key)) {
-      atomicMin(&ffirst[h], (int32_t)t);
-      return;
-    }
-    h = h + 1 == cap ? 0 : h + 1;
-  }
-}
-
-// keep[t] = non-degenerate and the first face of its (unordered) vertex triple
-__global__ __launch_bounds__(256) void k_faces_keep(const int32_t *__restrict__ faces, int64_t ntri,
-                                                   const int32_t *__restrict__ frep, const int32_t *__restrict__ ffirst,
-                                                   int64_t cap, uint8_t *__restrict__ keep) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= ntri) return;
-  if (tri_degenerate(faces + 3 * t)) {
-    keep[t] = 0;
-    return;
-  }
-  const Tri key = tri_sorted(faces + 3 * t);
-  int64_t h = (int64_t)(weld_hash(Cell{key.a, key.b, key.c}) % (uint64_t)cap);
-  while (!tri_same(tri_sorted(faces + 3 * (int64_t)frep[h]), key)) h = h + 1 == cap ? 0 : h + 1;
-  keep[t] = ffirst[h] == (int32_t)t;
-}
-
-SGNN_EXPORT int sgnn_weld_number(const int32_t *sel, int64_t n, int32_t *newid, sgnn_stream_t stream) {
-  SGNN_CHECK_ARG(n >= 0);
-  if (n == 0) return SGNN_OK;
-  SGNN_CHECK_ARG(sel && newid);
-  SGNN_LAUNCH(k_weld_number, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sel, n, newid);
-  SGNN_CHECK_LAUNCH();
-  return SGNN_OK;
-}
-
-SGNN_EXPORT int sgnn_mesh_faces(const int32_t *creator_of, const int32_t *newid, int64_t ntri, int32_t *faces,
-                                int32_t *frep, int32_t *ffirst, int64_t cap, uint8_t *keep, sgnn_stream_t stream) {
-  SGNN_CHECK_ARG(ntri >= 0 && cap >= sgnn_weld_slots(ntri) && frep && ffirst);
-  hipStream_t s = (hipStream_t)stream;
-  SGNN_HIP_TRY(hipMemsetAsync(frep, 0xFF, (size_t)cap * sizeof(int32_t), s));
-  SGNN_HIP_TRY(hipMemsetAsync(ffirst, 0x7F, (size_t)cap * sizeof(int32_t), s));
-  if (ntri == 0) return SGNN_OK;
-  SGNN_CHECK_ARG(creator_of && newid && faces && keep);
-  const dim3 grid((unsigned)((ntri + 255) / 256));
-  SGNN_LAUNCH(k_faces_remap, dim3((unsigned)((3 * ntri + 255) / 256)), dim3(256), 0, s, creator_of, newid, ntri,
-                     faces);
-  SGNN_LAUNCH(k_faces_insert, grid, dim3(256), 0, s, (const int32_t *)faces, ntri, frep, ffirst, cap);
-  SGNN_LAUNCH(k_faces_keep, grid, dim3(256), 0, s, (const int32_t *)faces, ntri, (const int32_t *)frep,
-                     (const int32_t *)ffirst, cap, keep);
-  SGNN_CHECK_LAUNCH();
-  return SGNN_OK;
-}
-
-// out rows p < n: rows sel[p] of a (., 3) float / uint8 / int32 array
-template <typename T>
-__global__ __launch_bounds__(256) void k_take3(const T *__restrict__ src, const int32_t *__restrict__ sel, int64_t n,
-                                              T *__restrict__ dst) {
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= 3 * n) return;
-  dst[e] = src[3 * (int64_t)sel[e / 3] + e % 3];
-}
-
-SGNN_EXPORT int sgnn_take_rows3(const void *src, int elem_bytes, const int32_t *sel, int64_t n, void *dst,
-                                sgnn_stream_t stream) {
-  SGNN_CHECK_ARG(n >= 0 && (elem_bytes == 1 || elem_bytes == 4));
-  if (n == 0) return SGNN_OK;
-  SGNN_CHECK_ARG(src && sel && dst);
-  const dim3 grid((unsigned)((3 * n + 255) / 256));
-  if (elem_bytes == 4)
-    SGNN_LAUNCH((k_take3<uint32_t>), grid, dim3(256), 0, (hipStream_t)stream, (const uint32_t *)src, sel, n,
-                       (uint32_t *)dst);
-  else
-    SGNN_LAUNCH((k_take3<uint8_t>), grid, dim3(256), 0, (hipStream_t)stream, (const uint8_t *)src, sel, n,
-                       (uint8_t *)dst);
   SGNN_CHECK_LAUNCH();
   return SGNN_OK;
 }

@@ -6,20 +6,21 @@
 // sums are taken by one lane, in ascending corner number.
 //
 //   k_simp_keys     one thread per vertex: the 63-bit cell key (rule 1), or SIMP_EMPTY and the status word
-//   k_simp_insert   64-bit-key open addressing: atomicCAS on the key, atomicMin on the smallest member index (rule 2)
+//   k_simp_insert   the first-member table of first_table.h with the 64-bit key in the slot (rule 2)
 //   k_simp_lookup   first_of[i] = smallest member of vertex i's cluster, is_first[i]
 //   k_simp_corners  one thread per face: corner_first[3t+k] = first_of[faces[t][k]] (rule 3), bad faces -> status
 //   (the caller numbers the clusters with sgnn_compact_mask + sgnn_weld_number and remaps / de-duplicates the faces
-//    with sgnn_mesh_faces, the table code marching cubes uses: rule 6)
+//    with sgnn_mesh_faces, the shared code of mesh_tables.hip: rule 6)
 //   k_simp_mark     used[c] = 1 for every cluster a kept face refers to
 //   k_simp_place    one lane per surviving cluster: rule 4's sums over its corners, rule 5's solve, the vertex
 //
 // All passes are gathers bound by latency; k_simp_place reads nine floats per corner and keeps ~16 doubles per lane.
 #include "common.h"
+#include "first_table.h"
 
 namespace {
 
-constexpr uint64_t SIMP_EMPTY = 0xFFFFFFFFFFFFFFFFull;     // no key has bit 63 set
+constexpr uint64_t SIMP_EMPTY = SLOT_EMPTY<uint64_t>;    // no key has bit 63 set
 constexpr float SIMP_CELLS_AXIS = 2097152.0f;              // 2^21 cells per axis
 constexpr int64_t LIMIT = (int64_t)1 << 31;
 
@@ -47,20 +48,8 @@ __global__ __launch_bounds__(256) void k_simp_insert(const uint64_t *__restrict_
   if (i >= nv) return;
   const uint64_t key = keys[i];
   if (key == SIMP_EMPTY) return;
-  int64_t h = (int64_t)(sgnn_hash64(key) % (uint64_t)cap);
-  for (;;) {      // ends: the table has more slots than keys
-    uint64_t cur = __hip_atomic_load(&tkeys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == SIMP_EMPTY) {
-      const uint64_t old = (uint64_t)atomicCAS(reinterpret_cast<unsigned long long *>(tkeys) + h,
-                                               (unsigned long long)SIMP_EMPTY, (unsigned long long)key);
-      cur = old == SIMP_EMPTY ? key : old;
-    }
-    if (cur == key) {
-      atomicMin(&tfirst[h], (int32_t)i);
-      return;
-    }
-    h = h + 1 == cap ? 0 : h + 1;
-  }
+  first_insert(tkeys, tfirst, cap, (int64_t)(sgnn_hash64(key) % (uint64_t)cap), (int32_t)i, key,
+               [&](uint64_t k) { return k == key; });
 }
 
 __global__ __launch_bounds__(256) void k_simp_lookup(const uint64_t *__restrict__ keys, int64_t nv,
@@ -72,9 +61,8 @@ __global__ __launch_bounds__(256) void k_simp_lookup(const uint64_t *__restrict_
   const uint64_t key = keys[i];
   int32_t f = -1;
   if (key != SIMP_EMPTY) {
-    int64_t h = (int64_t)(sgnn_hash64(key) % (uint64_t)cap);
-    while (tkeys[h] != key) h = h + 1 == cap ? 0 : h + 1;     // the key was inserted by the previous kernel
-    f = tfirst[h];
+    const int64_t home = (int64_t)(sgnn_hash64(key) % (uint64_t)cap);
+    f = tfirst[first_find<true>(tkeys, cap, home, [&](uint64_t k) { return k == key; })];  // present: k_simp_insert ran first
   }
   first_of[i] = f;
   is_first[i] = f == (int32_t)i;

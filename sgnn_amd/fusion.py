@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib, data
+from ._glue import compact, device as _device, host as _host, to_device as _to_device
 
 # struct sgnn_fuse_frame (include/sgnn_hip.h)
 FRAME_DTYPE = np.dtype([('m', '<f4', (12,)), ('intr', '<f4', (4,)), ('box', '<i4', (6,)), ('offset', '<i8')])
@@ -28,22 +29,6 @@ assert FRAME_DTYPE.itemsize == 96
 # 1 -> 108 ms, 8 -> 71, 64 -> 66, all -> 53 (profiles/fusion_bench.json)
 DEFAULT_CHUNK = 0
 EMPTY_BOX = np.array([0, -1, 0, -1, 0, -1], dtype=np.int32)
-
-
-def _device(device=None):
-    _lib.require_gpu()
-    return torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-
-
-def _to_device(x, dtype, dev):
-    t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
-    return t.to(device=dev, dtype=dtype).contiguous()
-
-
-def _host(x, dtype):
-    if torch.is_tensor(x):
-        x = x.detach().cpu().numpy()
-    return np.ascontiguousarray(np.asarray(x, dtype=dtype))
 
 
 def round_half_away(x):
@@ -249,10 +234,7 @@ class TSDFVolume(object):
         mask = torch.empty(n, dtype=torch.uint8, device=self.device)
         _lib.call('sgnn_fuse_flag', self._sdf.data_ptr(), dx, dy, dz, float(keep_abs), float(truncation),
                   float(self.voxel_size), int(max_z), mask.data_ptr())
-        sel = torch.empty(n, dtype=torch.int32, device=self.device)
-        count = torch.zeros(1, dtype=torch.int64, device=self.device)
-        ws = torch.empty(max(int(_lib.query('sgnn_compact_ws_bytes', n)), 1), dtype=torch.uint8, device=self.device)
-        _lib.call('sgnn_compact_mask', mask.data_ptr(), n, sel.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel())
+        sel, count = compact(mask, n, self.device, read=False)
         return sel, count, int(count.item())
 
     def sparse(self, trunc_factor=6.0):

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._glue import compact, dedup_faces, number, take3
 
 WELD_THRESH = 0.00001          # marching_cubes.cpp:489,568 merge_close_vertices(results, 0.00001f, true)
 MAX_SWEEPS = 100000
@@ -20,15 +21,6 @@ MAX_SWEEPS = 100000
 
 def _count(t):
     return int(t.item())
-
-
-def _compact(mask, n, dev):
-    sel = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    cnt = torch.zeros(1, dtype=torch.int64, device=dev)
-    wsb = _lib.query('sgnn_compact_ws_bytes', n)
-    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
-    _lib.call('sgnn_compact_mask', _lib.ptr(mask), n, _lib.ptr(sel), _lib.ptr(cnt), _lib.ptr(ws), wsb)
-    return sel, _count(cnt)
 
 
 def triangle_soup(tsdf, colors, isovalue, truncation, thresh):
@@ -81,24 +73,12 @@ def clean_mesh(verts, vcols, thresh=WELD_THRESH):
     is_creator = torch.empty(max(nv, 1), dtype=torch.uint8, device=dev)
     _lib.call('sgnn_weld_lookup', _lib.ptr(cells), nv, _lib.ptr(rep), _lib.ptr(first), _lib.ptr(state), cap,
               _lib.ptr(creator_of), _lib.ptr(is_creator))
-    sel, n_new = _compact(is_creator, nv, dev)
-    newid = torch.empty(max(nv, 1), dtype=torch.int32, device=dev)
-    _lib.call('sgnn_weld_number', _lib.ptr(sel), n_new, _lib.ptr(newid))
-    out_v = torch.empty((n_new, 3), dtype=torch.float32, device=dev)
-    out_c = torch.empty((n_new, 3), dtype=torch.uint8, device=dev)
-    _lib.call('sgnn_take_rows3', _lib.ptr(verts), 4, _lib.ptr(sel), n_new, _lib.ptr(out_v))
-    _lib.call('sgnn_take_rows3', _lib.ptr(vcols), 1, _lib.ptr(sel), n_new, _lib.ptr(out_c))
-    fcap = _lib.query('sgnn_weld_slots', ntri)
-    faces = torch.empty((max(ntri, 1), 3), dtype=torch.int32, device=dev)
-    frep = torch.empty(fcap, dtype=torch.int32, device=dev)
-    ffirst = torch.empty(fcap, dtype=torch.int32, device=dev)
-    keep = torch.empty(max(ntri, 1), dtype=torch.uint8, device=dev)
-    _lib.call('sgnn_mesh_faces', _lib.ptr(creator_of), _lib.ptr(newid), ntri, _lib.ptr(faces), _lib.ptr(frep),
-              _lib.ptr(ffirst), fcap, _lib.ptr(keep))
-    fsel, n_faces = _compact(keep, ntri, dev)
-    out_f = torch.empty((n_faces, 3), dtype=torch.int32, device=dev)
-    _lib.call('sgnn_take_rows3', _lib.ptr(faces), 4, _lib.ptr(fsel), n_faces, _lib.ptr(out_f))
-    return out_v, out_c, out_f
+    sel, n_new = compact(is_creator, nv, dev)
+    newid = number(sel, n_new, nv, dev)                         # read at creators only
+    out_v, out_c = take3(verts, 4, sel, n_new, torch.float32), take3(vcols, 1, sel, n_new, torch.uint8)
+    faces, keep = dedup_faces(creator_of, newid, ntri, dev)     # queued with the two gathers before the next read-back
+    fsel, n_faces = compact(keep, ntri, dev)
+    return out_v, out_c, take3(faces, 4, fsel, n_faces, torch.int32)
 
 
 def run_marching_cubes(tsdf, colors, isovalue, truncation, thresh):

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .fusion import _device, _host, _to_device
+from ._glue import device as _device, host as _host, to_device as _to_device
 
 STATUS_INDEX_RANGE = 1      # SGNN_STATUS_COORD_RANGE
 MAX_CELLS_AXIS = 1024       # cells per axis and in all that an index accepts (rule 5)

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .fusion import _device, _host, _to_device
+from ._glue import device as _device, host as _host, to_device as _to_device
 
 # struct sgnn_raycast_frame (include/sgnn_hip.h)
 FRAME_DTYPE = np.dtype([('g', '<f4', (12,)), ('intr', '<f4', (4,))])

@@ -23,9 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .fusion import _device, _to_device
-from .marching_cubes import _compact
-from .components import _take3
+from ._glue import compact, dedup_faces, device as _device, number, take3, to_device as _to_device
 
 STATUS_RANGE = 1            # SGNN_STATUS_COORD_RANGE
 CELLS_AXIS = 1 << 21        # cells per axis that a key holds
@@ -33,16 +31,6 @@ LIMIT = 2 ** 31
 PLACEMENTS = ('mean', 'quadric')
 
 Simplified = namedtuple('Simplified', 'verts faces colors vertex_map face_map')
-
-
-def _compact_dev(mask, n, dev):
-    """marching_cubes._compact without its read-back: (sel, count as a device int64[1])."""
-    sel = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    cnt = torch.zeros(1, dtype=torch.int64, device=dev)
-    wsb = _lib.query('sgnn_compact_ws_bytes', n)
-    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
-    _lib.call('sgnn_compact_mask', _lib.ptr(mask), n, _lib.ptr(sel), _lib.ptr(cnt), _lib.ptr(ws), wsb)
-    return sel, cnt
 
 
 def _inputs(verts, faces, colors=None):
@@ -78,7 +66,7 @@ def _origin(v, origin):
 
 
 class _Clusters:
-    """Rules 1, 2, 3 and 6 up to the kept-face mask, with nothing read back: a cluster is named by its first member.
+    """Rules 1, 2 and 3 with nothing read back: a cluster is named by its first member (rule 6 is _glue.dedup_faces).
     A vertex or a face that raises a status word is passed over by every stage, so the words can be read late."""
 
     def __init__(self, v, f, origin, cell):
@@ -108,18 +96,6 @@ class _Clusters:
             raise _lib.SgnnError('face index out of range [0, %d)' % self.nv)
         return count
 
-    def keep_mask(self, newid):
-        """sgnn_mesh_faces on the corners: (faces (F, 3) as newid of their clusters, keep (F,) u8)."""
-        nt, dev = self.nt, self.dev
-        fcap = _lib.query('sgnn_weld_slots', nt)
-        cfaces = torch.empty((max(nt, 1), 3), dtype=torch.int32, device=dev)
-        frep = torch.empty(fcap, dtype=torch.int32, device=dev)
-        ffirst = torch.empty(fcap, dtype=torch.int32, device=dev)
-        keep = torch.empty(max(nt, 1), dtype=torch.uint8, device=dev)
-        _lib.call('sgnn_mesh_faces', _lib.ptr(self.corner_first), _lib.ptr(newid), nt, _lib.ptr(cfaces), _lib.ptr(frep),
-                  _lib.ptr(ffirst), fcap, _lib.ptr(keep))
-        return cfaces, keep
-
 
 def cluster(verts, faces, cell=0.06, colors=None, placement='quadric', origin=None):
     """Simplified(verts, faces, colors, vertex_map, face_map) of the mesh clustered on a grid of pitch cell.
@@ -138,18 +114,16 @@ def cluster(verts, faces, cell=0.06, colors=None, placement='quadric', origin=No
     nv, nt = int(v.shape[0]), int(f.shape[0])
     org = _origin(v, origin)
     cl = _Clusters(v, f, org, cell)
-    sel, nclust = _compact_dev(cl.is_first, nv, dev)           # stable: sel[k] = first member of cluster k
+    sel, nclust = compact(cl.is_first, nv, dev, read=False)    # stable: sel[k] = first member of cluster k
     nclust = cl.read(nclust)
-    rank = torch.empty(max(nv, 1), dtype=torch.int32, device=dev)      # read at first members only
-    _lib.call('sgnn_weld_number', _lib.ptr(sel), nclust, _lib.ptr(rank))
-    cfaces, keep = cl.keep_mask(rank)
-    fsel, n_faces = _compact(keep, nt, dev)
-    kept = _take3(cfaces, 4, fsel, n_faces, torch.int32)       # surviving faces in cluster numbers
+    rank = number(sel, nclust, nv, dev)                        # read at first members only
+    cfaces, keep = dedup_faces(cl.corner_first, rank, nt, dev)      # faces in cluster numbers, kept-face mask
+    fsel, n_faces = compact(keep, nt, dev)
+    kept = take3(cfaces, 4, fsel, n_faces, torch.int32)        # surviving faces in cluster numbers
     used = torch.zeros(max(nclust, 1), dtype=torch.uint8, device=dev)
     _lib.call('sgnn_simp_mark', _lib.ptr(kept), n_faces, nclust, _lib.ptr(used))
-    csel, nout = _compact(used, nclust, dev)                   # output vertex p is cluster csel[p]
-    newc = torch.full((max(nclust, 1),), -1, dtype=torch.int32, device=dev)
-    _lib.call('sgnn_weld_number', _lib.ptr(csel), nout, _lib.ptr(newc))
+    csel, nout = compact(used, nclust, dev)                    # output vertex p is cluster csel[p]
+    newc = number(csel, nout, nclust, dev, fill=-1)
     out_v = torch.empty((nout, 3), dtype=torch.float32, device=dev)
     out_c = None if col is None else torch.empty((nout, 3), dtype=torch.uint8, device=dev)
     if nout:
@@ -175,8 +149,8 @@ def count_faces(verts, faces, cell, origin=None):
 def _count(v, f, org, cell, identity):
     """Rules 1, 2 and 6 with a cluster named by its first member (the kept faces are the same); one read-back."""
     cl = _Clusters(v, f, org, cell)
-    _, keep = cl.keep_mask(identity)
-    return cl.read(_compact_dev(keep, cl.nt, cl.dev)[1])
+    _, keep = dedup_faces(cl.corner_first, identity, cl.nt, cl.dev)
+    return cl.read(compact(keep, cl.nt, cl.dev, read=False)[1])
 
 
 def cell_for_faces(verts, faces, target_faces, lo=None, hi=None, iters=16):

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib, raycast
-from .fusion import _device, _host, _to_device
+from ._glue import device as _device, host as _host, to_device as _to_device
 
 # struct sgnn_track_pair (include/sgnn_hip.h)
 PAIR_DTYPE = np.dtype([('t', '<f4', (12,)), ('intr_live', '<f4', (4,)), ('intr_model', '<f4', (4,)),

@@ -950,6 +950,43 @@ int sgnn_simp_place(const float *verts, int nverts, const int32_t *faces, int nt
                     uint8_t *out_colors, sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Triangle meshes to signed distance volumes (sgnn_amd.voxelize; rules in INTEGRATION.md section L).  The mesh is in
+ * grid coordinates (voxel (i, j, k) has its centre at the integer point); records, boxes and usable come from
+ * sgnn_meshdist_pack.  Volumes are (dz, dy, dx), x fastest, every dimension in [1, 65535] and fewer than 2^31 voxels;
+ * band in [0, 65535] voxels.  Bricks are 8 x 8 x 8 voxels, brick (bx, by, bz) has the number (bz * nby + by) * nbx + bx
+ * with nb = ceil(d / 8).  The caller chains the stages:
+ *   sgnn_vox_grid_coords  -> out (nv,3) f32 = world2grid (host, 12 floats: rows 0..2 of the 4x4) applied to verts,
+ *                            ((m0 x + m1 y) + m2 z) + m3 per row
+ *   sgnn_vox_bricks_count -> counts[brick] += faces whose dilated box touches the brick (the caller zeroes counts)
+ *   (caller: offsets = exclusive scan of counts; bricks = sgnn_compact_mask(counts > 0))
+ *   sgnn_vox_bricks_fill  -> refs[offsets[brick] + k] = face, k from the zeroed cursor array; order inside a list is
+ *                            not defined and does not matter
+ *   sgnn_vox_normals      -> the pseudo-normal sums of rule 5 in 2^-32 fixed point: vsum (nverts,3) i64 per vertex,
+ *                            esum (cap,3) i64 per slot of the edge table ekeys (cap) i64 / efirst (cap) i32, all
+ *                            initialised here; cap >= sgnn_weld_slots(3 * ntri)
+ *   sgnn_vox_nearest      -> dist f32 (signed, in voxels) and face i32 of every voxel of the nbricks listed bricks:
+ *                            one workgroup per brick, face records staged through LDS SGNN_VOX_BATCH at a time.  Voxels
+ *                            beyond the band get +inf and -1; voxels of other bricks are not written (the caller fills
+ *                            them with +inf and -1 beforehand).  flip != 0 negates the pseudo-normals.
+ *   sgnn_vox_tsdf         -> sdf[i] = dist[i] * voxel_size where face[i] >= 0, -inf elsewhere; weight[i] u8 = 1 / 0
+ * Integer atomics only: the same input gives the same bits.
+ * ------------------------------------------------------------------------- */
+#define SGNN_VOX_BATCH 128
+int sgnn_vox_grid_coords(const float *verts, int64_t nv, const float *world2grid, float *out, sgnn_stream_t stream);
+int sgnn_vox_bricks_count(const float *boxes, int ntri, float band, int dx, int dy, int dz, int32_t *counts,
+                          sgnn_stream_t stream);
+int sgnn_vox_bricks_fill(const float *boxes, int ntri, float band, int dx, int dy, int dz, const int32_t *offsets,
+                         int32_t *cursor, int32_t *refs, sgnn_stream_t stream);
+int sgnn_vox_normals(const float *records, const int32_t *faces, const uint8_t *usable, int ntri, int nverts,
+                     int64_t *vsum, int64_t *ekeys, int32_t *efirst, int64_t *esum, int64_t cap, sgnn_stream_t stream);
+int sgnn_vox_nearest(const float *records, const float *boxes, const int32_t *faces, const int32_t *offsets,
+                     const int32_t *refs, const int32_t *bricks, int nbricks, int dx, int dy, int dz, float band,
+                     int flip, const int64_t *vsum, const int64_t *ekeys, const int64_t *esum, int64_t cap, float *dist,
+                     int32_t *face, sgnn_stream_t stream);
+int sgnn_vox_tsdf(const float *dist, const int32_t *face, int64_t n, float voxel_size, float *sdf, uint8_t *weight,
+                  sgnn_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Evaluation metrics on the device.
  * ------------------------------------------------------------------------- */
 /* IoU ingredients of one hierarchy level (torch/loss.py:84-120 compute_iou_sparse_dense, fed as in

@@ -167,6 +167,13 @@ PROTOTYPES = {
     'sgnn_simp_mark': (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp]),
     'sgnn_simp_place': (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_i32,
                                 c_vp, c_vp, c_vp]),
+    'sgnn_vox_grid_coords': (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp]),
+    'sgnn_vox_bricks_count': (c_i32, [c_vp, c_i32, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    'sgnn_vox_bricks_fill': (c_i32, [c_vp, c_i32, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    'sgnn_vox_normals': (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'sgnn_vox_nearest': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_vp, c_vp,
+                                 c_vp, c_i64, c_vp, c_vp, c_vp]),
+    'sgnn_vox_tsdf': (c_i32, [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp]),
     'sgnn_iou_counts': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'sgnn_l1_tgtsurf_ws_bytes': (c_i64, []),
     'sgnn_l1_tgtsurf': (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp, c_i64, c_vp]),

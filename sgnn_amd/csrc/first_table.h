@@ -5,8 +5,8 @@
 //
 // A slot (type T, memset to 0xFF = SLOT_EMPTY; first[] to 0x7F) holds what its claimant stored: the claimant's own index
 // where the keys sit in an array written before the inserts (int32: the vertex weld of mc.hip, the duplicate-face set of
-// mesh_tables.hip), or the 64-bit key itself (simplify.hip's clusters).  match(slot value) says whether a slot belongs to
-// the caller's key.
+// mesh_tables.hip), or the 64-bit key itself (simplify.hip's clusters, voxelize.hip's edges).  match(slot value) says
+// whether a slot belongs to the caller's key.
 #pragma once
 #include "common.h"
 

@@ -8,10 +8,13 @@
 #include <initializer_list>
 #include "common.h"
 
-// vector width (floats) usable for contiguous rows of c floats at these base pointers: float4 needs c % 4 == 0 and every
-// base 16-byte aligned (a contiguous view that starts at an odd float offset of a larger buffer takes the scalar form)
-static inline int row_vec(int c, std::initializer_list<const void *> ptrs) {
+// vector width (floats) usable for rows of c floats with these row strides (floats) at these base pointers: float4 needs
+// c % 4 == 0 and every stride and base 16-byte aligned (a view that starts at an odd float offset of a larger buffer takes
+// the scalar form).  Contiguous rows (stride c) pass no strides: c % 4 == 0 covers them.
+static inline int row_vec(int c, std::initializer_list<int64_t> lds, std::initializer_list<const void *> ptrs) {
   if (c % 4) return 1;
+  for (int64_t l : lds)
+    if (l % 4) return 1;
   for (const void *p : ptrs)
     if ((uintptr_t)p & 15) return 1;
   return 4;
@@ -176,7 +179,7 @@ SGNN_EXPORT int sgnn_gather_rows(const float *src, int c, const int32_t *idx, in
   SGNN_CHECK_ARG(c >= 1 && m >= 0);
   if (m == 0) return SGNN_OK;
   SGNN_CHECK_ARG(src && idx && dst);
-  const int vec = row_vec(c, {src, dst}), cq = c / vec;
+  const int vec = row_vec(c, {}, {src, dst}), cq = c / vec;
   ROWS_LAUNCH(k_gather_rows, vec, m * cq, stream, src, cq, idx, m, dst);
   SGNN_CHECK_LAUNCH();
   return SGNN_OK;
@@ -235,32 +238,13 @@ __global__ __launch_bounds__(256) void k_add_ld(const float *__restrict__ a, int
   }
 }
 
-static inline bool ld_vec4(int c, std::initializer_list<int64_t> lds, std::initializer_list<const void *> ptrs) {
-  if (c % 4) return false;
-  for (int64_t l : lds)
-    if (l % 4) return false;
-  for (const void *p : ptrs)
-    if ((uintptr_t)p & 15) return false;
-  return true;
-}
-
-#define ROWS_LAUNCH_V(KERNEL, vec4, total_groups, stream, ...)                                         \
-  do {                                                                                                 \
-    const int grid_ = sgnn_grid_for((total_groups), 256, 4096);                                        \
-    if (vec4)                                                                                          \
-      SGNN_LAUNCH((KERNEL<4>), dim3(grid_), dim3(256), 0, (hipStream_t)(stream), __VA_ARGS__);  \
-    else                                                                                               \
-      SGNN_LAUNCH((KERNEL<1>), dim3(grid_), dim3(256), 0, (hipStream_t)(stream), __VA_ARGS__);  \
-  } while (0)
-
 int sgnn_gather_rows_ld(const float *src, int64_t ld_src, int c, const int32_t *idx, int64_t m, float *dst,
                         int64_t ld_dst, sgnn_stream_t stream, const int64_t *n_dev) {
   SGNN_CHECK_ARG(c >= 1 && m >= 0 && ld_src >= c && ld_dst >= c);
   if (m == 0) return SGNN_OK;
   SGNN_CHECK_ARG(src && idx && dst);
-  const bool v4 = ld_vec4(c, {ld_src, ld_dst}, {src, dst});
-  const int cq = v4 ? c / 4 : c;
-  ROWS_LAUNCH_V(k_gather_rows_ld, v4, m * cq, stream, src, ld_src, cq, idx, m, dst, ld_dst, n_dev);
+  const int vec = row_vec(c, {ld_src, ld_dst}, {src, dst}), cq = c / vec;
+  ROWS_LAUNCH(k_gather_rows_ld, vec, m * cq, stream, src, ld_src, cq, idx, m, dst, ld_dst, n_dev);
   SGNN_CHECK_LAUNCH();
   return SGNN_OK;
 }
@@ -270,9 +254,8 @@ int sgnn_gather_sum_ld(const float *src, int64_t ld_src, int c, const int32_t *t
   SGNN_CHECK_ARG(c >= 1 && n_out >= 0 && K >= 1 && ld >= n_out && ld_src >= c && ld_dst >= c);
   if (n_out == 0) return SGNN_OK;
   SGNN_CHECK_ARG(src && table && dst);
-  const bool v4 = ld_vec4(c, {ld_src, ld_dst}, {src, dst});
-  const int cq = v4 ? c / 4 : c;
-  ROWS_LAUNCH_V(k_gather_sum_ld, v4, n_out * cq, stream, src, ld_src, cq, table, ld, K, n_out, dst, ld_dst, n_dev);
+  const int vec = row_vec(c, {ld_src, ld_dst}, {src, dst}), cq = c / vec;
+  ROWS_LAUNCH(k_gather_sum_ld, vec, n_out * cq, stream, src, ld_src, cq, table, ld, K, n_out, dst, ld_dst, n_dev);
   SGNN_CHECK_LAUNCH();
   return SGNN_OK;
 }
@@ -282,9 +265,8 @@ int sgnn_add_ld(const float *a, int64_t lda, const float *b, int64_t ldb, int64_
   SGNN_CHECK_ARG(c >= 1 && n >= 0 && lda >= c && ldb >= c && ldy >= c);
   if (n == 0) return SGNN_OK;
   SGNN_CHECK_ARG(a && b && y);
-  const bool v4 = ld_vec4(c, {lda, ldb, ldy}, {a, b, y});
-  const int cq = v4 ? c / 4 : c;
-  ROWS_LAUNCH_V(k_add_ld, v4, n * cq, stream, a, lda, b, ldb, n, cq, y, ldy, n_dev);
+  const int vec = row_vec(c, {lda, ldb, ldy}, {a, b, y}), cq = c / vec;
+  ROWS_LAUNCH(k_add_ld, vec, n * cq, stream, a, lda, b, ldb, n, cq, y, ldy, n_dev);
   SGNN_CHECK_LAUNCH();
   return SGNN_OK;
 }
@@ -310,7 +292,7 @@ SGNN_EXPORT int sgnn_gather_rows_dn(const float *src, int c, const int32_t *idx,
   SGNN_CHECK_ARG(c >= 1 && m_cap >= 0 && m_dev);
   if (m_cap == 0) return SGNN_OK;
   SGNN_CHECK_ARG(src && idx && dst);
-  const int vec = row_vec(c, {src, dst}), cq = c / vec;
+  const int vec = row_vec(c, {}, {src, dst}), cq = c / vec;
   ROWS_LAUNCH(k_gather_rows_dn, vec, m_cap * cq, stream, src, cq, idx, m_dev, m_cap, dst);
   SGNN_CHECK_LAUNCH();
   return SGNN_OK;
@@ -341,7 +323,7 @@ SGNN_EXPORT int sgnn_scatter_rows(const float *src, int c, const int32_t *idx, i
   }
   if (m == 0 || n_dst == 0) return SGNN_OK;
   SGNN_CHECK_ARG(src && idx);
-  const int vec = row_vec(c, {src, dst}), cq = c / vec;
+  const int vec = row_vec(c, {}, {src, dst}), cq = c / vec;
   ROWS_LAUNCH(k_scatter_rows, vec, m * cq, stream, src, cq, idx, m, dst, m_dev);
   SGNN_CHECK_LAUNCH();
   return SGNN_OK;
@@ -371,7 +353,7 @@ SGNN_EXPORT int sgnn_gather_sum(const float *src, int c, const int32_t *table, i
   SGNN_CHECK_ARG(c >= 1 && n_out >= 0 && K >= 1 && ld >= n_out);
   if (n_out == 0) return SGNN_OK;
   SGNN_CHECK_ARG(src && table && dst);
-  const int vec = row_vec(c, {src, dst}), cq = c / vec;
+  const int vec = row_vec(c, {}, {src, dst}), cq = c / vec;
   ROWS_LAUNCH(k_gather_sum, vec, n_out * cq, stream, src, cq, table, ld, K, n_out, dst);
   SGNN_CHECK_LAUNCH();
   return SGNN_OK;
@@ -393,7 +375,7 @@ SGNN_EXPORT int sgnn_repeat_rows(const float *src, int c, int64_t n, int rep, fl
   SGNN_CHECK_ARG(c >= 1 && n >= 0 && rep >= 1);
   if (n == 0) return SGNN_OK;
   SGNN_CHECK_ARG(src && dst);
-  const int vec = row_vec(c, {src, dst}), cq = c / vec;
+  const int vec = row_vec(c, {}, {src, dst}), cq = c / vec;
   ROWS_LAUNCH(k_repeat_rows, vec, n * rep * cq, stream, src, cq, n, rep, dst);
   SGNN_CHECK_LAUNCH();
   return SGNN_OK;
@@ -427,7 +409,7 @@ int sgnn_sum_groups_dn(const float *src, int c, int64_t n, int rep, float *dst, 
   SGNN_CHECK_ARG(c >= 1 && n >= 0 && rep >= 1);
   if (n == 0) return SGNN_OK;
   SGNN_CHECK_ARG(src && dst);
-  const int vec = row_vec(c, {src, dst}), cq = c / vec;
+  const int vec = row_vec(c, {}, {src, dst}), cq = c / vec;
   ROWS_LAUNCH(k_sum_groups, vec, n * cq, stream, src, cq, n, rep, dst, n_dev);
   SGNN_CHECK_LAUNCH();
   return SGNN_OK;

@@ -384,7 +384,7 @@ TILE = {'conv_small': 0}
 WIDE = {'conv_small_rows': 0, 'conv_wide_epi': 1, 'conv_unrolled': 1}
 
 # seeds of the real cases: the first of 0, 1, 2, ... that passes the ReLU guard (test_prog_ref.py)
-SEEDS = {'u3': 3, 'u3_kept_middle': 3, 'stage_lin_add': 1, 'output_without_gradient': 2}
+SEEDS = {'u3': 3, 'u3_kept_middle': 3, 'stage_lin_add': 1, 'output_without_gradient': 2, 'join_bn_5_8': 2}
 
 
 def cases():
@@ -396,6 +396,9 @@ def cases():
     for name, c, d in (('residual_16_16', 16, 16), ('residual_8_12', 8, 12), ('residual_5_7', 5, 7)):
         out.append(_residual(name, c, d, True, s(name)))
     out.append(_join('join_bn_5_7', 5, 5, 7, True, s('join_bn_5_7')))
+    # 8 un-pooled channels at column 5 of 13-float rows: a stride that is no multiple of 4 forces the scalar form of the
+    # strided gather and of its gradient's gather-sum on a width that would otherwise take float4
+    out.append(_join('join_bn_5_8', 8, 5, 8, True, s('join_bn_5_8')))
     out.append(_u3('u3', s('u3')))
     out.append(_u3('u3_kept_middle', s('u3_kept_middle'), keep_mid=True))
     out.append(_no_gout(s('output_without_gradient')))

@@ -268,8 +268,8 @@ def test_executor_against_fp64_interpreter(tune, name):
     assert not bad, '\n'.join(bad)
 
 
-CAPACITY_CASES = ['join_int_8_12', 'nested_joins', 'two_readers', 'stage_int', 'residual_8_12', 'join_bn_5_7', 'u3',
-                  'stage_lin_add']
+CAPACITY_CASES = ['join_int_8_12', 'nested_joins', 'two_readers', 'stage_int', 'residual_8_12', 'join_bn_5_7', 'join_bn_5_8',
+                  'u3', 'stage_lin_add']
 
 
 @pytest.mark.parametrize('fused', [1, 0])

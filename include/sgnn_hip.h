@@ -557,7 +557,8 @@ int sgnn_loss_levels_bwd(const int64_t *levels, int n, const float *coef_host, c
  *         3-4x smaller for a U-Net stage (whole-scene inference, BASELINE configs[3]);
  * mode 3: the same with bf16 storage (sgnn_prog_forward with training = 2 | 4).  Still counted in floats: a buffer of
  *         n rows takes ceil(n * ld / 2) floats, ld = its channels rounded up to a multiple of 8 bf16 elements; LINEAR
- *         outputs stay fp32 (ld = channels).  sgnn_prog_buffer_offset: infer = 2 gives this layout's offsets. */
+ *         outputs stay fp32 (ld = channels).  sgnn_prog_buffer_offset: infer = 2 gives this layout's offsets
+ *         (for an external: the offset of its bf16 copy, -1 if it has none). */
 int64_t sgnn_prog_arena_floats(const int32_t *ops, int nops, const int32_t *bufs, int nbuf, int n_ext,
                                const int64_t *lev_n, int nlev, const int32_t *keep, int mode);
 int64_t sgnn_prog_ws_bytes(const int32_t *ops, int nops, const int64_t *lev_n, int nlev);

@@ -567,8 +567,9 @@ SGNN_EXPORT int64_t sgnn_prog_ws_bytes(const int32_t *ops, int nops, const int64
   return ws_need(v);
 }
 
-// float offset of buffer `b` inside an arena (so the host layer can hand out views); -1 for externals.  infer: 0 training
-// layout, 1 inference layout, 2 bf16 inference layout (rows of round-up-to-8 bf16 elements; LINEAR outputs stay fp32)
+// float offset of buffer `b` inside an arena (so the host layer can hand out views); -1 for externals, except that the
+// bf16 layout reports where an external's bf16 copy lives (-1 if it has none).  infer: 0 training layout, 1 inference
+// layout, 2 bf16 inference layout (rows of round-up-to-8 bf16 elements; LINEAR outputs stay fp32)
 SGNN_EXPORT int64_t sgnn_prog_buffer_offset(const int32_t *ops, int nops, const int32_t *bufs, int nbuf, int n_ext,
                                             const int64_t *lev_n, int nlev, const int32_t *keep, int infer, int b) {
   View v{ops, nullptr, nops, bufs, nbuf, n_ext, lev_n, nullptr, nullptr, nullptr, nullptr, nullptr, nlev};
@@ -577,7 +578,8 @@ SGNN_EXPORT int64_t sgnn_prog_buffer_offset(const int32_t *ops, int nops, const 
   Plan P;
   make_plan(v, keep, P, kind);
   Layout L;
-  if (make_layout(v, P, L, keep) != 0 || b < 0 || b >= nbuf || b < n_ext) return -1;
+  if (make_layout(v, P, L, keep) != 0 || b < 0 || b >= nbuf) return -1;
+  if (b < n_ext) return L.shadow[b] ? L.buf_off[b] : -1;
   return P.root[b] == b ? L.buf_off[b] : -1;      // buffers the caller keeps are never views
 }
 

@@ -4,12 +4,19 @@ alone: small hand-built op lists (Net), their sites, data and the plan each is m
 Integer cases (SUBM, DOWN, UNPOOL, ADD, JOIN, CONCAT_IN, EXPAND only; data and weights in {-1, 0, 1}, weights and output
 gradients thinned out so that every sum of |terms| stays below 2^24) are compared bit for bit; real cases (anything with
 BatchNorm or a head) against the bars of test_gpu_prog_fp64.py.  Seeds of the real cases are chosen so that no BatchNorm
-pre-activation of the fp64 reference lies near zero (test_prog_ref.py asserts it)."""
+pre-activation of the fp64 reference lies near zero (test_prog_ref.py asserts it).
+
+test_gpu_prog_bf16.py runs the same cases through the bf16 executor: there the integer cases are the exact ones (every
+stored value is a bf16 value, test_prog_ref.py asserts it under the data of data(geom, bf16=True))."""
 import numpy as np
 import torch
 
 OP_SUBM, OP_DOWN, OP_UNPOOL, OP_BN, OP_ADD, OP_JOIN, OP_CONCAT_IN, OP_EXPAND, OP_LINEAR = range(9)
 OPW = 12
+# externals of the exact cases under the bf16 data: 1 + 2^-8 lies halfway between the bf16 values 1 and 1 + 2^-7 and
+# rounds to the even one, 1; a sum of three unrounded ones, 3 + 3 x 2^-8, rounds to 3 + 2^-6 and gives a reader away
+# that took the fp32 tensor where it should have taken the bf16 copy
+BF16_EXT_SCALE = 1.0 + 2.0 ** -8
 
 
 class Net(object):
@@ -126,14 +133,15 @@ class Case(object):
     gradient is not wanted; plan: what sgnn_prog_plan must report with the fusions on, {'add_dst': {op: v}, 'join_view':
     {op: v}, 'lin_bn': {op: v}, 'root' / 'col' / 'ld': {buffer: v}} (what is not listed: add_dst / lin_bn -1, join_view 0,
     every buffer its own root at column 0 with ld = channels); zero_slots: parameter slots whose gradient must be exactly
-    zero; extra_rows: rows of the named source classes."""
+    zero; extra_rows: rows of the named source classes.  bf16_density: the weight density of an integer case's data for
+    the bf16 executor (data(geom, bf16=True)); the plan of the bf16 layout follows from `plan` (expected_plan)."""
 
     def __init__(self, name, net, integer, keep, gout, plan, side=16, occupancy=0.3, seed=0, gext_null=(), zero_slots=(),
-                 extra_rows=None, knobs=None, empty=False):
+                 extra_rows=None, knobs=None, empty=False, bf16_density=0.25):
         self.name, self.net, self.integer, self.keep, self.gout, self.plan = name, net, integer, list(keep), list(gout), plan
         self.side, self.occupancy, self.seed = side, occupancy, seed
         self.gext_null, self.zero_slots, self.extra_rows = list(gext_null), list(zero_slots), dict(extra_rows or {})
-        self.knobs, self.empty = knobs, empty
+        self.knobs, self.empty, self.bf16_density = knobs, empty, bf16_density
 
     def coords(self):
         """Level-0 sites [z, y, x, b] of one batch entry inside side^3 (side even at every pyramid level)."""
@@ -155,8 +163,11 @@ class Case(object):
             r[cid] = 8 * geom.n[0] if name == 'child' else self.extra_rows[name]
         return r
 
-    def data(self, geom):
-        """(params, ext, idx, gouts) as CPU fp32 tensors, from the case's seed alone."""
+    def data(self, geom, bf16=False):
+        """(params, ext, idx, gouts) as CPU fp32 tensors, from the case's seed alone.  bf16: the data of the bf16 executor's
+        test, which differs for integer cases only: their weights are thinned out to bf16_density, so that every value
+        the program stores is exactly a bf16 value (test_prog_ref.py), and their externals are +-BF16_EXT_SCALE instead
+        of +-1: fp32 values that are no bf16 values and that the executor must round (to +-1) before use."""
         net = self.net
         rows = self.rows(geom)
         gen = torch.Generator().manual_seed(77 + self.seed)
@@ -169,7 +180,7 @@ class Case(object):
         for kind, shape in net.slots:
             if self.integer:
                 assert kind == 'w'
-                params.append(ints(shape, 0.25))
+                params.append(ints(shape, self.bf16_density if bf16 else 0.25))
             elif kind == 'w':
                 params.append(torch.randn(shape, generator=gen) * (2.0 / (shape[0] * shape[1])) ** 0.5)
             elif kind == 'gamma':
@@ -184,6 +195,8 @@ class Case(object):
         for b in range(net.n_ext):
             shape = (rows[net.bufs[b][0]], net.bufs[b][1])
             ext.append(ints(shape, 1.0) if self.integer else torch.randn(shape, generator=gen))
+            if self.integer and bf16:
+                ext[-1] = ext[-1] * BF16_EXT_SCALE
         idx = []
         for s in range(net.n_idx):
             src = [o[1 + k] if k < 2 else o[8] for o in net.ops if o[0] == OP_CONCAT_IN for k in range(3) if o[9 + k] == s]
@@ -242,6 +255,48 @@ def _join(name, c, c0, c1, bn, seed=0, knobs=None):
     return Case(name, n, not bn, [j, z], [j, z],
                 {'join_view': {jop: 1}, 'root': {a: j, u: j}, 'col': {u: c0}, 'ld': {a: c0 + c1, u: c0 + c1}}, seed=seed,
                 knobs=knobs)
+
+
+def _join_col(name, c0, bn, second='conv', seed=0, bf16_density=0.25):
+    """An in-place JoinTable whose second input starts at column c0 = 6, 10 or 12: in bf16 rows that is byte 12, 20 or 24
+    (= 12, 4, 8 mod 16), where a view is aligned to a dword or to 8 bytes only (join_int_8_12 reaches byte 16).  The
+    integer form writes there from a convolution epilogue, the BatchNorm form from BatchNorm's apply pass or, with
+    second = 'unpool', from the UnPooling gather."""
+    n = Net()
+    x = n.ext(0, 8)
+    a = n.bn(n.subm(x, c0)) if bn else n.unpool(n.down(x, c0))
+    if second == 'unpool':
+        b = n.unpool(n.bn(n.down(x, 12)))
+    else:
+        b = n.subm(x, 12)
+        if bn:
+            b = n.bn(b)
+    j = n.join(a, b)
+    z = n.subm(j, 8)
+    n.finish()
+    jop = len(n.ops) - 2
+    return Case(name, n, not bn, [j, z], [j, z],
+                {'join_view': {jop: 1}, 'root': {a: j, b: j}, 'col': {b: c0}, 'ld': {a: c0 + 12, b: c0 + 12}}, seed=seed,
+                bf16_density=bf16_density)
+
+
+def _nested_6_12(name, bn, seed=0, bf16_density=0.25):
+    """[[6 | 12] | 8]: the inner JoinTable is in place (second input at column 6), the outer one copies (a storage root is
+    never itself a view, see _nested_joins) and so puts its second input at column 6 + 12 = 18 of 26-channel rows — byte
+    36 of a bf16 row."""
+    n = Net()
+    x = n.ext(0, 8)
+    if bn:
+        a, b, c = n.bn(n.subm(x, 6)), n.unpool(n.bn(n.down(x, 12))), n.bn(n.subm(x, 8))
+    else:
+        a, b, c = n.unpool(n.down(x, 6)), n.subm(x, 12), n.subm(x, 8)
+    j1 = n.join(a, b)
+    j2 = n.join(j1, c)
+    z = n.subm(j2, 8)
+    n.finish()
+    jop = len(n.ops) - 3
+    return Case(name, n, not bn, [z], [z], {'join_view': {jop: 1, jop + 1: 0}, 'root': {a: j1, b: j1}, 'col': {b: 6},
+                                             'ld': {a: 18, b: 18}}, seed=seed, bf16_density=bf16_density)
 
 
 def _two_joins():
@@ -384,7 +439,8 @@ TILE = {'conv_small': 0}
 WIDE = {'conv_small_rows': 0, 'conv_wide_epi': 1, 'conv_unrolled': 1}
 
 # seeds of the real cases: the first of 0, 1, 2, ... that passes the ReLU guard (test_prog_ref.py)
-SEEDS = {'u3': 3, 'u3_kept_middle': 3, 'stage_lin_add': 1, 'output_without_gradient': 2, 'join_bn_5_8': 2}
+SEEDS = {'u3': 3, 'u3_kept_middle': 3, 'stage_lin_add': 1, 'output_without_gradient': 2, 'join_bn_5_8': 2,
+         'join_bn_12_12': 3}
 
 
 def cases():
@@ -399,6 +455,13 @@ def cases():
     # 8 un-pooled channels at column 5 of 13-float rows: a stride that is no multiple of 4 forces the scalar form of the
     # strided gather and of its gradient's gather-sum on a width that would otherwise take float4
     out.append(_join('join_bn_5_8', 8, 5, 8, True, s('join_bn_5_8')))
+    # in-place joins at the columns a bf16 view can get wrong
+    out += [_join_col('join_int_6_12', 6, False), _join_col('join_int_10_12', 10, False), _join_col('join_int_12_12', 12, False),
+            _nested_6_12('nested_int_6_12_8', False)]
+    out += [_join_col('join_bn_6_12', 6, True, seed=s('join_bn_6_12')),
+            _join_col('join_bn_10_12', 10, True, 'unpool', seed=s('join_bn_10_12')),
+            _join_col('join_bn_12_12', 12, True, seed=s('join_bn_12_12')),
+            _nested_6_12('nested_bn_6_12_8', True, seed=s('nested_bn_6_12_8'))]
     out.append(_u3('u3', s('u3')))
     out.append(_u3('u3_kept_middle', s('u3_kept_middle'), keep_mid=True))
     out.append(_no_gout(s('output_without_gradient')))
@@ -421,8 +484,11 @@ def case_names():
     return [c.name for c in cases()]
 
 
-def expected_plan(case, fused):
-    """Full arrays (skip is implied: fused AddTables and in-place JoinTables) from the case's sparse description."""
+def expected_plan(case, fused, bf16=False):
+    """Full arrays (skip is implied: fused AddTables and in-place JoinTables) from the case's sparse description.
+    bf16: the plan of the bf16 layout (sgnn_prog_plan mode 3) — the same, except that a JoinTable whose first input has an
+    odd channel count is not in place, and that every row stride counts bf16 elements and is rounded up to 8 (LINEAR
+    outputs stay fp32 rows of their own width)."""
     net = case.net
     nops, nbuf = len(net.ops), len(net.bufs)
     p = case.plan if fused else {}
@@ -431,6 +497,16 @@ def expected_plan(case, fused):
     for key, d in p.items():
         for k, v in d.items():
             want[key][k] = v
+    if bf16:
+        for i, o in enumerate(net.ops):
+            if want['join_view'][i] and o[6] % 2:
+                want['join_view'][i] = 0
+                for b in (o[1], o[2]):
+                    want['root'][b], want['col'][b] = b, 0
+        heads = set(o[3] for o in net.ops if o[0] == OP_LINEAR)
+        for b in range(nbuf):
+            ch = net.bufs[want['root'][b]][1]
+            want['ld'][b] = ch if want['root'][b] in heads else (ch + 7) // 8 * 8
     want['skip'] = [0] * nops
     for i in range(nops):
         if want['join_view'][i] or (i > 0 and want['add_dst'][i - 1] >= 0):
@@ -438,13 +514,15 @@ def expected_plan(case, fused):
     return want
 
 
-def read_plan(lib_query, case, rows, mode=0):
-    """sgnn_prog_plan for the case's descriptors as a dict of lists (the library's current switches apply)."""
+def read_plan(lib_query, case, rows, mode=0, keep=None):
+    """sgnn_prog_plan for the case's descriptors as a dict of lists (the library's current switches apply); keep: the
+    kept buffers, if not the case's own."""
     net = case.net
     nops, nbuf = len(net.ops), len(net.bufs)
     lev_n = np.ascontiguousarray(np.array(rows, dtype=np.int64))
+    kept = case.keep if keep is None else list(keep)
     keep = np.zeros(nbuf, dtype=np.int32)
-    keep[case.keep] = 1
+    keep[kept] = 1
     out = np.full(4 * nops + 3 * nbuf, -7, dtype=np.int32)
     rc = lib_query('sgnn_prog_plan', net.ops_np.ctypes.data, nops, net.bufs_np.ctypes.data, nbuf, net.n_ext, lev_n.ctypes.data,
                    net.n_classes, keep.ctypes.data, mode, out.ctypes.data)

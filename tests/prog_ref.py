@@ -19,6 +19,13 @@ honest fp32 evaluation of the same program makes (e_ref32 of the comparison rule
 run(..., abs_terms=True) evaluates the program on |parameters|, |inputs| and |output gradients|: every value it returns
 bounds the sum of |terms| behind the corresponding value of the plain run (integer cases: must stay below 2^24).
 
+run(..., storage='bf16') is the yardstick of the bf16 executor (forward_bf16, prog.hip; test_gpu_prog_bf16.py): forward
+only, eval, still float64 arithmetic, but every value is rounded to bf16 (to nearest even, straight from float64) where
+the executor stores one: convolution weights before use (EXPAND: its 27 weights, never the 64 pre-summed slices), the
+output of every op except LINEAR, and an external where an op other than CONCAT_IN reads it (CONCAT_IN rounds its
+result).  BatchNorm parameters, running statistics, head weights and biases stay as they are.  It never looks at the
+plan: it rounds behind every op, fused or not.
+
 `mutate` names one deliberate mistake (MUTATIONS); test_prog_ref.py shows that the comparison bars notice each of them.
 """
 import numpy as np
@@ -29,7 +36,17 @@ import conv_ref
 OP_SUBM, OP_DOWN, OP_UNPOOL, OP_BN, OP_ADD, OP_JOIN, OP_CONCAT_IN, OP_EXPAND, OP_LINEAR = range(9)
 
 MUTATIONS = ('add_drops_addend', 'join_swaps_columns', 'second_reader_gradient_dropped', 'running_stats_in_training',
-             'unpool_gradient_drops_a_child', 'head_data_gradient_dropped')
+             'unpool_gradient_drops_a_child', 'head_data_gradient_dropped', 'batch_stats_in_eval', 'external_not_rounded')
+
+
+def round_bf16(t):
+    """float64 -> the nearest bf16 value (ties to even), as float64; one rounding, not float64 -> float32 -> bf16.
+    (Normal range only: bf16 shares float32's exponent range, which no case comes near.)"""
+    assert t.dtype == torch.float64
+    u = t.detach().contiguous().clone().view(torch.int64)      # sign-magnitude: adding to the integer grows the magnitude
+    u += (1 << 44) - 1 + ((u >> 45) & 1)
+    u &= ~((1 << 45) - 1)
+    return u.view(torch.float64)
 
 
 class Geometry(object):
@@ -98,17 +115,21 @@ class _UnpoolDroppingAChild(torch.autograd.Function):
 
 
 def run(ops, bufs, opf, n_ext, rows, geom, params, ext, idx=(), training=True, gouts=None, dtype=torch.float64,
-        abs_terms=False, mutate=None):
+        abs_terms=False, mutate=None, storage=None):
     """ops (nops, 12), bufs (nbuf, 2), opf (nops, 4) as compiled; rows[c] the row count of rows class c; params[slot]
     tensors (None allowed); ext[b] the external tensors (None allowed); idx[i] integer arrays; gouts {buffer: gradient}.
     Returns a dict: 'bufs' (every buffer, detached), 'running' {slot: new value} (training), 'pre' {op: BatchNorm
     pre-activation t}, 'pre_mag' {op: |xhat gamma| + |beta|}, and with gouts 'gparams' [per slot, None for running
-    statistics] and 'gext' [per external]; gradients nothing reaches are zeros."""
+    statistics] and 'gext' [per external]; gradients nothing reaches are zeros.  storage='bf16': see the module's text."""
     assert mutate is None or mutate in MUTATIONS
+    assert storage in (None, 'bf16')
+    bf = storage == 'bf16'
+    assert not bf or (dtype == torch.float64 and gouts is None and not training)
+    rnd = round_bf16 if bf else (lambda t: t)
     ops, bufs, opf = np.asarray(ops), np.asarray(bufs), np.asarray(opf)
     prep = (lambda t: t.detach().abs()) if abs_terms else (lambda t: t.detach())
-    P = [None if p is None else prep(p.cpu()).to(dtype).clone().requires_grad_(True) for p in params]
-    E = [None if e is None else prep(e.cpu()).to(dtype).clone().requires_grad_(True) for e in ext]
+    P = [None if p is None else prep(p.cpu()).to(dtype).clone().requires_grad_(not bf) for p in params]
+    E = [None if e is None else prep(e.cpu()).to(dtype).clone().requires_grad_(not bf) for e in ext]
     I = [None if i is None else torch.as_tensor(i).cpu().long() for i in idx]
     B = [None] * bufs.shape[0]
     for b in range(n_ext):
@@ -116,8 +137,10 @@ def run(ops, bufs, opf, n_ext, rows, geom, params, ext, idx=(), training=True, g
     seen = set()
     out = {'running': {}, 'pre': {}, 'pre_mag': {}}
 
-    def read(b):
+    def read(b, raw=False):
         t = B[b]
+        if b < n_ext and not raw and mutate != 'external_not_rounded':
+            t = rnd(t)
         if mutate == 'second_reader_gradient_dropped' and b in seen:
             t = t.detach()
         seen.add(b)
@@ -126,9 +149,9 @@ def run(ops, bufs, opf, n_ext, rows, geom, params, ext, idx=(), training=True, g
     for i in range(ops.shape[0]):
         t, in0, in1, ob, par, lev, cin, cout, in2, ia, ib, ic = (int(v) for v in ops[i])
         if t == OP_SUBM:
-            y = _walk(read(in0), P[par], geom.nbr[lev])
+            y = _walk(read(in0), rnd(P[par]), geom.nbr[lev])
         elif t == OP_DOWN:
-            y = _walk(read(in0), P[par], geom.children[lev])
+            y = _walk(read(in0), rnd(P[par]), geom.children[lev])
         elif t == OP_UNPOOL:
             if mutate == 'unpool_gradient_drops_a_child':
                 y = _UnpoolDroppingAChild.apply(read(in0), geom.parent[lev], geom.children[lev])
@@ -140,7 +163,7 @@ def run(ops, bufs, opf, n_ext, rows, geom, params, ext, idx=(), training=True, g
             gamma, beta, rm, rv = P[par], P[par + 1], P[par + 2], P[par + 3]
             eps, mom, leak = float(opf[i][0]), float(opf[i][1]), float(opf[i][2])
             n = x.shape[0]
-            if training and mutate != 'running_stats_in_training':
+            if (training and mutate != 'running_stats_in_training') or mutate == 'batch_stats_in_eval':
                 if n:
                     mean = x.sum(0) / n
                     var = ((x - mean) ** 2).sum(0) / n
@@ -170,7 +193,7 @@ def run(ops, bufs, opf, n_ext, rows, geom, params, ext, idx=(), training=True, g
             for src, slot in ((in0, ia), (in1, ib), (in2, ic)):
                 if src < 0:
                     continue
-                x = read(src)
+                x = read(src, raw=True)
                 if slot < 0 or I[slot] is None:
                     assert x.shape[0] == n
                     parts.append(x)
@@ -185,7 +208,7 @@ def run(ops, bufs, opf, n_ext, rows, geom, params, ext, idx=(), training=True, g
                     parts.append(torch.where((j >= 0)[:, None], g, torch.zeros_like(g)))
             y = torch.cat(parts, 1)
         elif t == OP_EXPAND:
-            y = _walk(read(in0).repeat_interleave(8, 0), P[par], geom.child_nbr())
+            y = _walk(read(in0).repeat_interleave(8, 0), rnd(P[par]), geom.child_nbr())
         elif t == OP_LINEAR:
             x = read(in0)
             if mutate == 'head_data_gradient_dropped':
@@ -200,6 +223,8 @@ def run(ops, bufs, opf, n_ext, rows, geom, params, ext, idx=(), training=True, g
         else:
             raise ValueError('unknown op %d' % t)
         assert y.shape == (int(rows[bufs[ob][0]]), int(bufs[ob][1])), (i, tuple(y.shape), bufs[ob])
+        if t != OP_LINEAR:
+            y = rnd(y)
         B[ob] = y
     out['bufs'] = [None if t is None else t.detach() for t in B]
     if gouts is not None:
@@ -254,3 +279,24 @@ def floor_of(name, ops=None, slots=None):
 
 def bar(e_ref32, floor=conv_ref.BAR):
     return max(BAR_K * e_ref32, floor)
+
+
+# ---- the bar of the bf16 executor (rules in test_gpu_prog_bf16.py) ----
+
+# bar = max(BAR_K_BF16 x e_bf, 2^-8), both max-normalised: e_bf is the distance of the rounding interpreter
+# (storage='bf16') from the float64 one, 2^-8 one bf16 ulp of the tensor's largest value.  BAR_K_BF16 is the smallest
+# power of two that covers the worst err / e_bf measured with prog_fusion = 0: 1.149 (stage_lin_add, the BatchNorm
+# output behind the up-sampling convolution; profiles/prog_bf16_ratios.txt).  The fused and the keep-everything runs
+# meet the same k; the worst ratio of any run is 1.301.
+BAR_K_BF16 = 2
+BF16_ULP = 2.0 ** -8
+
+
+def bf16_externals(ext):
+    """fp32 externals rounded to bf16 by torch: what the fp64 interpreter is fed for an exact case, whose executor run
+    must equal it bit for bit although the externals themselves are no bf16 values (prog_cases.BF16_EXT_SCALE)."""
+    return [None if e is None else e.bfloat16().float() for e in ext]
+
+
+def bar_bf16(e_bf):
+    return max(BAR_K_BF16 * e_bf, BF16_ULP)

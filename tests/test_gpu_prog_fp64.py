@@ -94,21 +94,10 @@ def _table(t, K, ld):
     return out.cuda()
 
 
-def execute(case, lv, data, training, infer=False, capacity=None, counts=None):
-    """One forward (+ backward) call under the current switches.  capacity: factor by which every rows class is
-    over-allocated (lev_n = capacities, the live counts in device memory through lev_cnt; counts overrides them).
-    Returns a dict of CPU tensors: 'bufs' {buffer: all rows} (the kept buffers; every buffer the layout stores on its
-    own when nothing is fused), 'gparams', 'gext', 'params', 'live' {rows class: live rows}."""
-    L = _lib()
-    net, geom = case.net, lv.geom
-    params, ext, idx, gouts = data
-    live = case.rows(geom)
-    ncls, nops, nbuf, n_ext, nlev = net.n_classes, len(net.ops), len(net.bufs), net.n_ext, net.nlev
-    rows = list(live)
-    if capacity:
-        rows = [int(capacity * r) + 5 for r in live]
-        if 'child' in net.class_ids:
-            rows[net.class_ids['child']] = 8 * rows[0]
+def level_tables(net, geom, rows, live, capacity=None, counts=None):
+    """(lev_n, lev_ld, the five pointer tables of sgnn_prog_forward, the device tensors behind them) for `rows` rows per
+    class; capacity: the live counts (or `counts`) go to device memory through lev_cnt."""
+    ncls, nlev = net.n_classes, net.nlev
     lev_n = np.ascontiguousarray(np.array(rows, dtype=np.int64))
     lev_ld = np.zeros(ncls, dtype=np.int64)
     for l in range(nlev):
@@ -127,7 +116,31 @@ def execute(case, lv, data, training, infer=False, capacity=None, counts=None):
     cnt = []
     if capacity:
         cnt = [torch.tensor([live[c] if counts is None else counts[c]], dtype=torch.int64, device='cuda') for c in range(ncls)]
-    tabs = [_ptrs(pad(v)) for v in (nbr, children, ptable, parent, cnt)]
+    held = (nbr, children, ptable, parent, cnt)
+    return lev_n, lev_ld, [_ptrs(pad(v)) for v in held], held
+
+
+def capacity_rows(net, live, capacity):
+    rows = [int(capacity * r) + 5 for r in live]
+    if 'child' in net.class_ids:
+        rows[net.class_ids['child']] = 8 * rows[0]
+    return rows
+
+
+def execute(case, lv, data, training, infer=False, capacity=None, counts=None):
+    """One forward (+ backward) call under the current switches.  capacity: factor by which every rows class is
+    over-allocated (lev_n = capacities, the live counts in device memory through lev_cnt; counts overrides them).
+    Returns a dict of CPU tensors: 'bufs' {buffer: all rows} (the kept buffers; every buffer the layout stores on its
+    own when nothing is fused), 'gparams', 'gext', 'params', 'live' {rows class: live rows}."""
+    L = _lib()
+    net, geom = case.net, lv.geom
+    params, ext, idx, gouts = data
+    live = case.rows(geom)
+    ncls, nops, nbuf, n_ext, nlev = net.n_classes, len(net.ops), len(net.bufs), net.n_ext, net.nlev
+    rows = list(live)
+    if capacity:
+        rows = capacity_rows(net, live, capacity)
+    lev_n, lev_ld, tabs, held = level_tables(net, geom, rows, live, capacity, counts)
     nan = float('nan')
     P = [p.cuda().clone() for p in params]
     PG = [None if kind in ('rm', 'rv') else torch.full_like(p, nan) for p, (kind, _) in zip(P, net.slots)]

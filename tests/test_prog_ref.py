@@ -212,3 +212,180 @@ def test_every_case_takes_the_plan_it_is_meant_to_take(refs):
         for k, v in saved.items():
             _lib.tune(k, v)
     assert shown >= {'add_dst', 'no add_dst', 'lin_bn', 'no lin_bn', 'join_view', 'no join_view', 'unaligned join_view'}
+
+
+# ---- the bf16 executor's yardstick: the rounding interpreter (run(..., storage='bf16')), CPU alone ----
+
+@pytest.fixture(scope='module')
+def refs_bf16():
+    """name -> (case, geometry, data for the bf16 executor, fp64 eval run, rounding-interpreter eval run), computed once.
+    The fp64 run of an exact case is fed the externals rounded to bf16 (their own values are no bf16 values)."""
+    out = {}
+    for c in C.cases():
+        if c.knobs is not None:
+            continue
+        geom = R.oracle_geometry(c.coords(), c.net.nlev)
+        data = c.data(geom, bf16=True)
+        fed = (data[0], R.bf16_externals(data[1])) + tuple(data[2:]) if c.integer else data
+        out[c.name] = (c, geom, data, _fwd(c, geom, fed), _fwd(c, geom, data, storage='bf16'))
+    return out
+
+
+def _fwd(c, geom, data, **kw):
+    params, ext, idx, _ = data
+    n = c.net
+    return R.run(n.ops_np, n.bufs_np, n.opf_np, n.n_ext, c.rows(geom), geom, params, ext, idx, training=False, **kw)
+
+
+def test_round_bf16_is_torchs_rounding_without_the_float32_step():
+    gen = torch.Generator().manual_seed(0)
+    x = torch.randn(4096, generator=gen)
+    assert torch.equal(R.round_bf16(x.double()), x.bfloat16().double())
+    one, ulp = 1.0, 2.0 ** -7
+    ties = torch.tensor([one + ulp / 2, one + 3 * ulp / 2, -(one + ulp / 2), one + ulp / 2 + 2.0 ** -40, 0.0, 256.0, 257.0], dtype=torch.float64)
+    want = torch.tensor([one, one + 2 * ulp, -one, one + ulp, 0.0, 256.0, 256.0], dtype=torch.float64)
+    assert torch.equal(R.round_bf16(ties), want)
+    # float64 -> float32 -> bf16 would round 1 + ulp/2 + 2^-40 to a tie first and then down to 1
+    assert float(ties[3].float().bfloat16()) == one
+
+
+def test_exact_cases_store_nothing_but_bf16_values(refs_bf16):
+    """The exact cases of test_gpu_prog_bf16.py (the integer cases, under data(geom, bf16=True)): the externals are
+    +-(1 + 2^-8), which every reader must round to +-1; from there on every value the fp64 interpreter computes is a bf16
+    value, so no executor rounds again, whatever its plan, and the rounding interpreter (fed the unrounded externals)
+    reproduces the fp64 one (fed the rounded ones) bit for bit; the sums of |terms| stay below 2^24, so fp32
+    accumulation is exact in any order.  A condition on the inputs, not a tolerance."""
+    n_exact = 0
+    for name, (c, geom, data, r64, rbf) in refs_bf16.items():
+        if not c.integer:
+            continue
+        n_exact += 1
+        assert all(not torch.equal(e.bfloat16().float(), e) for e in data[1]), name
+        mag = _fwd(c, geom, (data[0], R.bf16_externals(data[1])) + tuple(data[2:]), abs_terms=True)
+        for b, (v, m) in enumerate(zip(r64['bufs'], mag['bufs'])):
+            assert torch.equal(R.round_bf16(v), v), '%s buffer %d: %d values are no bf16 values' % (
+                name, b, int((R.round_bf16(v) != v).sum()))
+            assert b < c.net.n_ext or torch.equal(rbf['bufs'][b], v), (name, b)
+            assert not v.numel() or float(m.max()) < conv_ref.EXACT_LIMIT, (name, b)
+        for p in data[0]:
+            assert torch.equal(R.round_bf16(p.double()), p.double()), name
+        assert all(float(r64['bufs'][b].abs().max()) > 0 for b in c.keep), name
+    assert n_exact >= 12
+
+
+BF16_BRANCHES = ('fused add', 'join view at byte 0 mod 16', 'join view at byte 4 mod 16', 'join view at byte 8 mod 16',
+                 'join view at byte 12 mod 16', 'join refused for odd cin', 'copying join writes at byte 4 mod 16',
+                 'shadowed external', 'external read only by CONCAT_IN', 'head on a bf16 buffer')
+
+
+def bf16_branches(c, plan, plan32):
+    """The branches of forward_bf16 a case reaches under `plan` (sgnn_prog_plan mode 3, fusions on)."""
+    net, out = c.net, set()
+    if max(plan['add_dst']) >= 0:
+        out.add('fused add')
+    for i, o in enumerate(net.ops):
+        if o[0] == C.OP_JOIN and plan['join_view'][i]:
+            out.add('join view at byte %d mod 16' % (2 * plan['col'][o[2]] % 16))
+        if o[0] == C.OP_JOIN and not plan['join_view'][i]:
+            if plan32['join_view'][i] and o[6] % 2:
+                out.add('join refused for odd cin')
+            if 2 * o[6] % 16 == 4:
+                out.add('copying join writes at byte 4 mod 16')
+        if o[0] == C.OP_LINEAR:
+            out.add('head on a bf16 buffer')
+    readers = dict((b, set(o[0] for o in net.ops if b in (o[1], o[2], o[8]))) for b in range(net.n_ext))
+    for b, r in readers.items():
+        if r - {C.OP_CONCAT_IN}:
+            out.add('shadowed external')
+        elif r:
+            out.add('external read only by CONCAT_IN')
+    return out
+
+
+def test_every_case_takes_its_bf16_plan(refs):
+    """sgnn_prog_plan mode 3 (host code): the plan of the bf16 layout is the fp32 plan, except that a JoinTable whose
+    first input has an odd channel count is not in place and that row strides are round8(channels) bf16 elements (fp32
+    rows of their own width for LINEAR outputs).  Between them the cases reach every branch of BF16_BRANCHES.  An
+    in-place view never lies inside another (see test_every_case_takes_the_plan_it_is_meant_to_take), so the column
+    6 + 12 of nested_*_6_12_8 is written by the copying JoinTable, not resolved through two views."""
+    from sgnn_amd import _lib
+    saved = _lib.tune('prog_fusion')
+    shown = {}
+    try:
+        for name, (c, geom, data, ref) in refs.items():
+            rows = c.rows(geom)
+            for fused in (1, 0):
+                _lib.tune('prog_fusion', fused)
+                got, want = C.read_plan(_lib.query, c, rows, 3), C.expected_plan(c, fused, bf16=True)
+                assert got == want, (name, fused, dict((k, (got[k], want[k])) for k in want if got[k] != want[k]))
+                heads = set(o[3] for o in c.net.ops if o[0] == C.OP_LINEAR)
+                assert all(v % 8 == 0 for b, v in enumerate(got['ld']) if got['root'][b] not in heads), name
+                if fused and not c.empty:
+                    for br in bf16_branches(c, got, C.read_plan(_lib.query, c, rows, 0)):
+                        shown.setdefault(br, name)
+    finally:
+        _lib.tune('prog_fusion', saved)
+    _lib.tune('prog_fusion', 1)
+    try:
+        for name in ('join_bn_5_7', 'join_bn_5_8'):
+            c, geom = refs[name][:2]
+            assert max(C.read_plan(_lib.query, c, c.rows(geom), 0)['join_view']) == 1, name
+            assert max(C.read_plan(_lib.query, c, c.rows(geom), 3)['join_view']) == 0, name
+    finally:
+        _lib.tune('prog_fusion', saved)
+    print('\n'.join('%-40s %s' % kv for kv in sorted(shown.items())))
+    assert set(shown) >= set(BF16_BRANCHES), set(BF16_BRANCHES) - set(shown)
+
+
+def _applies(mutation, net):
+    """add / join mutations: the program holds the op; external_not_rounded: an op other than CONCAT_IN reads an external."""
+    if mutation == 'external_not_rounded':
+        return any(o[0] != C.OP_CONCAT_IN and 0 <= b < net.n_ext for o in net.ops for b in (o[1], o[2]))
+    return any(o[0] == {'add_drops_addend': C.OP_ADD, 'join_swaps_columns': C.OP_JOIN}[mutation] for o in net.ops)
+
+
+@pytest.mark.parametrize('mutation', ['add_drops_addend', 'join_swaps_columns', 'external_not_rounded'])
+def test_bf16_mutation_changes_every_exact_case_it_applies_to(refs_bf16, mutation):
+    """Exact cases are compared bit for bit: the mutated rounding interpreter must differ from the fp64 run in a kept
+    buffer of every exact case it applies to.  (batch_stats_in_eval needs BatchNorm, which no exact case has.)"""
+    n = 0
+    for name, (c, geom, data, r64, rbf) in refs_bf16.items():
+        if not c.integer or not _applies(mutation, c.net):
+            continue
+        n += 1
+        bad = _fwd(c, geom, data, storage='bf16', mutate=mutation)
+        assert any(not torch.equal(bad['bufs'][b], r64['bufs'][b]) for b in c.keep), name
+    assert n >= 4
+
+
+def _bars_moved(c, geom, data, r64, rbf, mutation, against):
+    bad = _fwd(c, geom, data, storage='bf16', mutate=mutation)
+    return max(R.max_norm_error(bad['bufs'][b], against['bufs'][b]) / R.bar_bf16(R.max_norm_error(rbf['bufs'][b], r64['bufs'][b]))
+               for b in c.keep)
+
+
+@pytest.mark.parametrize('mutation,case', [('add_drops_addend', 'residual_8_12'), ('join_swaps_columns', 'join_bn_6_12'),
+                                           ('join_swaps_columns', 'u3'), ('batch_stats_in_eval', 'residual_8_12'),
+                                           ('batch_stats_in_eval', 'stage_lin_bn')])
+def test_bf16_mutation_moves_a_real_case_two_bars(refs_bf16, mutation, case):
+    """A mutated rounding interpreter stands in for a bf16 executor with that bug: some kept tensor of a real case moves
+    by at least 2 bars (prog_ref.bar_bf16) from the fp64 run.  batch_stats_in_eval is what a wrong choice of BatchNorm
+    statistics looks like in eval, the only mode the bf16 executor has: running_stats_in_training itself changes
+    nothing there (asserted)."""
+    c, geom, data, r64, rbf = refs_bf16[case]
+    assert _bars_moved(c, geom, data, r64, rbf, mutation, r64) >= 2.0
+    same = _fwd(c, geom, data, storage='bf16', mutate='running_stats_in_training')
+    assert all(torch.equal(same['bufs'][b], rbf['bufs'][b]) for b in c.keep)
+
+
+def test_an_unrounded_external_changes_the_real_cases_too(refs_bf16):
+    """external_not_rounded on real data is a sub-ulp change of the inputs that no tolerance tells from honest bf16
+    rounding (it moved no real case by 2 bars when measured: at most 1.13 x 2^-8 / bar from the fp64 run, 1.63 from the
+    rounding interpreter), so the exact cases carry its detection (above: their externals are no bf16 values).  As the
+    rule for a mutation that hides asks, test_gpu_prog_bf16.py holds the real cases to the rounding interpreter as well,
+    under the same bar.  Asserted here: the mutation is live on real data, it changes a kept tensor of some case."""
+    worst = 0.0
+    for name, (c, geom, data, r64, rbf) in refs_bf16.items():
+        if not (c.integer or c.empty):
+            worst = max(worst, _bars_moved(c, geom, data, r64, rbf, 'external_not_rounded', rbf))
+    assert worst > 0.0

@@ -467,26 +467,29 @@ int sgnn_linear_bwd(const float *x, const float *dy, int64_t n, int cin, const f
                     sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
- * Fused loss of one hierarchy level: sparse predictions vals (m, vstride) at
- * locs (m,4) int64 [z,y,x,b] against dense (B,1,d0,d1,d2) targets —
- *   out2[0] = mean over kept sites of w * BCE_with_logits(vals[:,occ_col], tgt_occ)   (torch/loss.py:58-82)
- *   out2[1] = mean over kept sites of w * |logt(vals[:,sdf_col]) - logt(tgt_sdf)|      (torch/loss.py:122-157)
+ * Fused hierarchical loss, all levels (n <= 5; a single level is n = 1) in two launches
+ * forward and one backward.  Per level: sparse predictions vals (m, vstride) at locs (m,4) int64 [z,y,x,b] against
+ * dense (B,1,d0,d1,d2) targets —
+ *   out2s[2l]   = mean over kept sites of w * BCE_with_logits(vals[:,occ_col], tgt_occ)   (torch/loss.py:58-82)
+ *   out2s[2l+1] = mean over kept sites of w * |logt(vals[:,sdf_col]) - logt(tgt_sdf)|      (torch/loss.py:122-157)
  * occ_col / sdf_col = -1 skips that term; weights / known may be NULL.
- * mask_mode 0: keep every site (UNK_ID occupancy targets count as 0); 1: keep tgt_occ != -1;
- * 2: keep known < 2.  sums (3 doubles, device) carries {sum bce, sum l1, kept} to the backward call,
- * which writes dvals (m, vstride) given gout2 = d loss / d out2 (device, 2 floats).
+ * mask_mode 0: keep every site (UNK_ID occupancy targets count as 0); 1: keep tgt_occ != -1; 2: keep known < 2.
+ * m_dev (device int64, may be NULL): the live row count in capacity mode; a level whose count is <= 0 contributes 0.
+ * sums (3n doubles, device) carries {sum bce, sum l1, kept} of every level to the backward call.
+ *   total  = sum_i coef[i] * out2s[i] over the slots with coef[i] != 0                     (torch/loss.py:160-199)
+ *   cur[l] = out2s[2l] + out2s[2l+1] restricted to those slots (the per-level values for logging)
+ *   dvals_l[:, occ_col] = g * coef[2l] * d bce_l,  dvals_l[:, sdf_col] = g * coef[2l+1] * d l1_l, other columns 0
+ * levels: HOST array of n x 16 int64 = {locs, vals, vstride, occ_col, sdf_col, tgt_occ, tgt_sdf, weights, known, d0, d1,
+ * d2, m, use_log, mask_mode, m_dev} (device pointers as integers); coef_host: 2n floats = (bce, l1) weight per level;
+ * out2s (2n floats), total, cur (n floats): device; g: device float = d loss / d total; dvals: HOST array of n device
+ * pointers, (m_l, vstride_l) floats each.  The fp64 two-stage reduction has a fixed order per level, which depends on
+ * that level's m alone: the same level gives the same bits whichever other levels share the call.
  * ------------------------------------------------------------------------- */
-int64_t sgnn_loss_ws_bytes(void);
-int sgnn_loss_level_fwd(const int64_t *locs, const float *vals, int vstride, int occ_col, int sdf_col,
-                        const float *tgt_occ, const float *tgt_sdf, const float *weights,
-                        const uint8_t *known, int d0, int d1, int d2, int64_t m, int use_log,
-                        int mask_mode, const int64_t *m_dev, double *sums, float *out2, void *ws, int64_t ws_bytes,
-                        sgnn_stream_t stream);
-int sgnn_loss_level_bwd(const int64_t *locs, const float *vals, int vstride, int occ_col, int sdf_col,
-                        const float *tgt_occ, const float *tgt_sdf, const float *weights,
-                        const uint8_t *known, int d0, int d1, int d2, int64_t m, int use_log,
-                        int mask_mode, const int64_t *m_dev, const double *sums, const float *gout2, float *dvals,
-                        sgnn_stream_t stream);
+int64_t sgnn_loss_multi_ws_bytes(void);
+int sgnn_loss_levels_fwd(const int64_t *levels, int n, const float *coef_host, double *sums, float *out2s, float *total,
+                         float *cur, void *ws, int64_t ws_bytes, sgnn_stream_t stream);
+int sgnn_loss_levels_bwd(const int64_t *levels, int n, const float *coef_host, const double *sums, const float *g,
+                         void *const *dvals, sgnn_stream_t stream);
 
 /* Targets of the hierarchical loss in three launches — compute_targets + compute_weights_missing_geo
  * (torch/loss.py:15-32, 35-48): tsdf = clamp(sdf, +-trunc); hier_last = tsdf; occ_last = |tsdf| < trunc with UNK_ID (-1)
@@ -499,23 +502,6 @@ int sgnn_loss_targets(const float *sdf, const uint8_t *known, const int64_t *inp
                       int d0, int d1, int d2, float trunc, int masking, float weight_missing_geo, int ncoarse,
                       void *const *hier_in, float *tsdf, float *hier_last, float *occ_last, float *w_last,
                       void *const *occ, void *const *w, void *const *hier, sgnn_stream_t stream);
-/* total = sum_i coef[i] * out2s[i] over the (bce, l1) pairs sgnn_loss_level_fwd produced for all levels (n <= 10
- * floats; coef is a HOST array, entries of unused slots 0), cur[l] = out2s[2l] + out2s[2l+1] restricted to used slots;
- * and the gradient fan-out g2[i] = g[0] * coef[i] that sgnn_loss_level_bwd consumes (torch/loss.py:160-199). */
-int sgnn_loss_combine(const float *out2s, const float *coef_host, int n, float *total, float *cur,
-                      sgnn_stream_t stream);
-int sgnn_loss_combine_bwd(const float *g, const float *coef_host, int n, float *g2, sgnn_stream_t stream);
-/* The same for ALL levels at once (n <= 5): two launches forward (sgnn_loss_level_fwd x n + sgnn_loss_combine), one
- * backward (sgnn_loss_combine_bwd + sgnn_loss_level_bwd x n); per level bit-identical to the entry points above.
- * levels: HOST array of n x 16 int64 = {locs, vals, vstride, occ_col, sdf_col, tgt_occ, tgt_sdf, weights, known, d0, d1,
- * d2, m, use_log, mask_mode, m_dev} (device pointers as integers); coef_host: 2n floats = (bce, l1) weight per level;
- * sums (3n doubles), out2s (2n floats), total, cur (n floats): device; g: device float = d loss / d total; dvals: HOST
- * array of n device pointers. */
-int64_t sgnn_loss_multi_ws_bytes(void);
-int sgnn_loss_levels_fwd(const int64_t *levels, int n, const float *coef_host, double *sums, float *out2s, float *total,
-                         float *cur, void *ws, int64_t ws_bytes, sgnn_stream_t stream);
-int sgnn_loss_levels_bwd(const int64_t *levels, int n, const float *coef_host, const double *sums, const float *g,
-                         void *const *dvals, sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Sparse-network programs: a static sub-network (what the reference composes from scn.Sequential /

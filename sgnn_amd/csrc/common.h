@@ -245,3 +245,21 @@ __device__ __forceinline__ int sgnn_block_rank256(bool flag, int *lds4, int &tot
   total = w0 + w1 + w2 + w3;
   return base + prefix;
 }
+
+// ---------------------------------------------------------------------------
+// block tree-sum of NC values per thread over the 256 threads of the block
+// ---------------------------------------------------------------------------
+// Thread t stores v[c] to sh[c][t]; after a barrier, for d = 128, 64, .., 1 every thread t < d adds sh[c][t + d] to
+// sh[c][t] (c = 0 .. NC-1), with a barrier after each d.  The totals are in sh[c][0] for every thread on return.
+// The pairing is fixed, so the same inputs give the same bits on every run: the deterministic reductions of loss.hip
+// and metrics.hip are tested bit for bit and rely on exactly this order.
+template <typename T, int NC>
+__device__ __forceinline__ void sgnn_block_sum256(T (&sh)[NC][256], const T (&v)[NC]) {
+  for (int c = 0; c < NC; ++c) sh[c][threadIdx.x] = v[c];
+  __syncthreads();
+  for (int d = 128; d > 0; d >>= 1) {
+    if (threadIdx.x < d)
+      for (int c = 0; c < NC; ++c) sh[c][threadIdx.x] += sh[c][threadIdx.x + d];
+    __syncthreads();
+  }
+}

@@ -1,10 +1,11 @@
-// Fused sparse-prediction vs dense-target loss of one hierarchy level (the caller
-// immediately downstream of the path): gathers the dense targets / weights / masks at the predicted
+// Fused sparse-prediction vs dense-target hierarchical loss (the caller immediately
+// downstream of the path): per level, gathers the dense targets / weights / masks at the predicted
 // sites and evaluates
 //     mean over kept sites of  w * BCE_with_logits(occ, tgt_occ)      torch/loss.py:58-82
 //     mean over kept sites of  w * | logt(sdf) - logt(tgt_sdf) |       torch/loss.py:122-157, :51-55
-// in one pass (the reference issues ~25 torch ops and an int32 volume per level and step).
-// HBM-bound gather + deterministic fp64 two-stage reduction; backward is a second gather pass.
+// in one pass (the reference issues ~25 torch ops and an int32 volume per level and step), all levels in one
+// submission: two launches forward, one backward.  HBM-bound gather + deterministic fp64 two-stage reduction;
+// backward is a second gather pass.
 #include "common.h"
 
 #define LOSS_MAX_BLOCKS 512
@@ -59,84 +60,12 @@ __device__ __forceinline__ bool loss_site(const LossArgs &a, int64_t r, float &b
   return true;
 }
 
-__global__ __launch_bounds__(256) void k_loss_partial(LossArgs a, double *__restrict__ partial) {
-  __shared__ double sh[3][256];
-  double s_b = 0.0, s_l = 0.0, s_n = 0.0;
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  const int64_t m = sgnn_dyn_n(a.m, a.m_dev);
-  for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < m; r += stride) {
-    float bce, l1, db, dl;
-    if (loss_site(a, r, bce, l1, db, dl)) {
-      s_b += (double)bce;
-      s_l += (double)l1;
-      s_n += 1.0;
-    }
-  }
-  sh[0][threadIdx.x] = s_b;
-  sh[1][threadIdx.x] = s_l;
-  sh[2][threadIdx.x] = s_n;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if (threadIdx.x < d)
-      for (int c = 0; c < 3; ++c) sh[c][threadIdx.x] += sh[c][threadIdx.x + d];
-    __syncthreads();
-  }
-  if (threadIdx.x < 3) partial[blockIdx.x * 3 + threadIdx.x] = sh[threadIdx.x][0];
-}
-
-// sums[0..2] = {sum bce, sum l1, kept count}; out2 = {bce mean, l1 mean} (0/0 = nan like an empty mean)
-__global__ __launch_bounds__(256) void k_loss_finalize(const double *__restrict__ partial, int nblk,
-                                                      double *__restrict__ sums, float *__restrict__ out2,
-                                                      const int64_t *m_dev) {
-  __shared__ double sh[3][256];
-  double s[3] = {0.0, 0.0, 0.0};
-  for (int b = threadIdx.x; b < nblk; b += 256)
-    for (int c = 0; c < 3; ++c) s[c] += partial[b * 3 + c];
-  for (int c = 0; c < 3; ++c) sh[c][threadIdx.x] = s[c];
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if (threadIdx.x < d)
-      for (int c = 0; c < 3; ++c) sh[c][threadIdx.x] += sh[c][threadIdx.x + d];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    sums[0] = sh[0][0];
-    sums[1] = sh[1][0];
-    sums[2] = sh[2][0];
-    // capacity mode with no predicted site at all: the reference skips the level (torch/loss.py:166, len(...) == 0)
-    const bool empty = m_dev && *m_dev <= 0;
-    out2[0] = empty ? 0.f : (float)(sh[0][0] / sh[2][0]);
-    out2[1] = empty ? 0.f : (float)(sh[1][0] / sh[2][0]);
-  }
-}
-
-// dvals[r][occ_col] = g[0] * dbce / kept,  dvals[r][sdf_col] = g[1] * dl1 / kept; other columns zero
-__global__ __launch_bounds__(256) void k_loss_bwd(LossArgs a, const double *__restrict__ sums,
-                                                 const float *__restrict__ gout2, float *__restrict__ dvals) {
-  const double kept = sums[2];
-  const float g0 = (float)((double)gout2[0] / kept), g1 = (float)((double)gout2[1] / kept);
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  const int64_t m = sgnn_dyn_n(a.m, a.m_dev);
-  for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < m; r += stride) {
-    float bce, l1, db, dl;
-    const bool keep = loss_site(a, r, bce, l1, db, dl);
-    for (int c = 0; c < a.vstride; ++c) {
-      float v = 0.f;
-      if (keep && c == a.occ_col) v = g0 * db;
-      if (keep && c == a.sdf_col) v = g1 * dl;
-      dvals[r * a.vstride + c] = v;
-    }
-  }
-}
-
 static int loss_blocks(int64_t m) {
   int64_t b = (m + 1023) / 1024;
   if (b < 1) b = 1;
   if (b > LOSS_MAX_BLOCKS) b = LOSS_MAX_BLOCKS;
   return (int)b;
 }
-
-SGNN_EXPORT int64_t sgnn_loss_ws_bytes(void) { return (int64_t)LOSS_MAX_BLOCKS * 3 * sizeof(double) + 64; }
 
 static int fill_args(LossArgs &a, const int64_t *locs, const float *vals, int vstride, int occ_col, int sdf_col,
                      const float *tgt_occ, const float *tgt_sdf, const float *weights, const uint8_t *known, int d0,
@@ -152,47 +81,9 @@ static int fill_args(LossArgs &a, const int64_t *locs, const float *vals, int vs
   return 0;
 }
 
-SGNN_EXPORT int sgnn_loss_level_fwd(const int64_t *locs, const float *vals, int vstride, int occ_col, int sdf_col,
-                                    const float *tgt_occ, const float *tgt_sdf, const float *weights,
-                                    const uint8_t *known, int d0, int d1, int d2, int64_t m, int use_log,
-                                    int mask_mode, const int64_t *m_dev, double *sums, float *out2, void *ws,
-                                    int64_t ws_bytes, sgnn_stream_t stream) {
-  LossArgs a;
-  SGNN_CHECK_ARG(fill_args(a, locs, vals, vstride, occ_col, sdf_col, tgt_occ, tgt_sdf, weights, known, d0, d1, d2, m,
-                           use_log, mask_mode, m_dev) == 0);
-  SGNN_CHECK_ARG(sums && out2);
-  if (!ws || ws_bytes < sgnn_loss_ws_bytes()) {
-    sgnn_set_error("sgnn_loss_level_fwd: workspace too small");
-    return SGNN_ENOWS;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const int nblk = loss_blocks(m);
-  SGNN_LAUNCH(k_loss_partial, dim3(nblk), dim3(256), 0, s, a, (double *)ws);
-  SGNN_LAUNCH(k_loss_finalize, dim3(1), dim3(256), 0, s, (const double *)ws, nblk, sums, out2, m_dev);
-  SGNN_CHECK_LAUNCH();
-  return SGNN_OK;
-}
-
-SGNN_EXPORT int sgnn_loss_level_bwd(const int64_t *locs, const float *vals, int vstride, int occ_col, int sdf_col,
-                                    const float *tgt_occ, const float *tgt_sdf, const float *weights,
-                                    const uint8_t *known, int d0, int d1, int d2, int64_t m, int use_log,
-                                    int mask_mode, const int64_t *m_dev, const double *sums, const float *gout2,
-                                    float *dvals, sgnn_stream_t stream) {
-  LossArgs a;
-  SGNN_CHECK_ARG(fill_args(a, locs, vals, vstride, occ_col, sdf_col, tgt_occ, tgt_sdf, weights, known, d0, d1, d2, m,
-                           use_log, mask_mode, m_dev) == 0);
-  if (m == 0) return SGNN_OK;
-  SGNN_CHECK_ARG(sums && gout2 && dvals);
-  SGNN_LAUNCH(k_loss_bwd, dim3(sgnn_grid_for(m, 256, 2048)), dim3(256), 0, (hipStream_t)stream, a, sums, gout2,
-                     dvals);
-  SGNN_CHECK_LAUNCH();
-  return SGNN_OK;
-}
-
 // ---------------------------------------------------------------------------
-// All levels of the hierarchical loss in one submission: sgnn_loss_level_fwd x n + sgnn_loss_combine as TWO launches,
-// sgnn_loss_combine_bwd + sgnn_loss_level_bwd x n as ONE (17 -> 3 launches per training step).  Per level the same
-// block partition, the same summation order and therefore the same bits as the per-level entry points.
+// Up to LOSS_MAX_LEVELS levels per call (blockIdx.y = level; a single level is n = 1).  A level's sums depend only on
+// its own sites and its own block partition loss_blocks(m), never on which other levels share the launch.
 // ---------------------------------------------------------------------------
 #define LOSS_MAX_LEVELS 5
 struct LossMulti {
@@ -205,54 +96,42 @@ struct LossOut {
   float *dvals[LOSS_MAX_LEVELS];
 };
 
-__global__ __launch_bounds__(256) void k_loss_partial_multi(LossMulti m, double *__restrict__ partial) {
+__global__ __launch_bounds__(256) void k_loss_partial(LossMulti m, double *__restrict__ partial) {
   __shared__ double sh[3][256];
   const int l = blockIdx.y;
   const LossArgs &a = m.a[l];
   if ((int)blockIdx.x >= m.nblk[l]) return;
-  double s_b = 0.0, s_l = 0.0, s_n = 0.0;
+  double s[3] = {0.0, 0.0, 0.0};   // sum bce, sum l1, kept count
   const int64_t stride = (int64_t)m.nblk[l] * 256;
   const int64_t rows = sgnn_dyn_n(a.m, a.m_dev);
   for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < rows; r += stride) {
     float bce, l1, db, dl;
     if (loss_site(a, r, bce, l1, db, dl)) {
-      s_b += (double)bce;
-      s_l += (double)l1;
-      s_n += 1.0;
+      s[0] += (double)bce;
+      s[1] += (double)l1;
+      s[2] += 1.0;
     }
   }
-  sh[0][threadIdx.x] = s_b;
-  sh[1][threadIdx.x] = s_l;
-  sh[2][threadIdx.x] = s_n;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if (threadIdx.x < d)
-      for (int c = 0; c < 3; ++c) sh[c][threadIdx.x] += sh[c][threadIdx.x + d];
-    __syncthreads();
-  }
+  sgnn_block_sum256(sh, s);
   if (threadIdx.x < 3) partial[((size_t)l * LOSS_MAX_BLOCKS + blockIdx.x) * 3 + threadIdx.x] = sh[threadIdx.x][0];
 }
 
-// one workgroup: per-level totals and means, then total = sum coef * out2 and the per-level values for logging
-__global__ __launch_bounds__(256) void k_loss_finalize_multi(const double *__restrict__ partial, LossMulti m,
-                                                            double *__restrict__ sums, float *__restrict__ out2s,
-                                                            float *__restrict__ total, float *__restrict__ cur) {
+// one workgroup: per level sums[3l..] = {sum bce, sum l1, kept count} and out2s[2l..] = {bce mean, l1 mean} (0/0 = nan
+// like an empty mean), then total = sum coef * out2 and the per-level values for logging
+__global__ __launch_bounds__(256) void k_loss_finalize(const double *__restrict__ partial, LossMulti m,
+                                                      double *__restrict__ sums, float *__restrict__ out2s,
+                                                      float *__restrict__ total, float *__restrict__ cur) {
   __shared__ double sh[3][256];
   for (int l = 0; l < m.n; ++l) {
     double s[3] = {0.0, 0.0, 0.0};
     for (int b = threadIdx.x; b < m.nblk[l]; b += 256)
       for (int c = 0; c < 3; ++c) s[c] += partial[((size_t)l * LOSS_MAX_BLOCKS + b) * 3 + c];
-    for (int c = 0; c < 3; ++c) sh[c][threadIdx.x] = s[c];
-    __syncthreads();
-    for (int d = 128; d > 0; d >>= 1) {
-      if (threadIdx.x < d)
-        for (int c = 0; c < 3; ++c) sh[c][threadIdx.x] += sh[c][threadIdx.x + d];
-      __syncthreads();
-    }
+    sgnn_block_sum256(sh, s);
     if (threadIdx.x == 0) {
       sums[3 * l + 0] = sh[0][0];
       sums[3 * l + 1] = sh[1][0];
       sums[3 * l + 2] = sh[2][0];
+      // capacity mode with no predicted site at all: the reference skips the level (torch/loss.py:166, len(...) == 0)
       const bool empty = m.a[l].m_dev && *m.a[l].m_dev <= 0;
       out2s[2 * l] = empty ? 0.f : (float)(sh[0][0] / sh[2][0]);
       out2s[2 * l + 1] = empty ? 0.f : (float)(sh[1][0] / sh[2][0]);
@@ -269,8 +148,9 @@ __global__ __launch_bounds__(256) void k_loss_finalize_multi(const double *__res
   }
 }
 
-__global__ __launch_bounds__(256) void k_loss_bwd_multi(LossMulti m, const double *__restrict__ sums,
-                                                       const float *__restrict__ g, LossOut o) {
+// dvals[r][occ_col] = g * coef[2l] * dbce / kept,  dvals[r][sdf_col] = g * coef[2l+1] * dl1 / kept; other columns zero
+__global__ __launch_bounds__(256) void k_loss_bwd(LossMulti m, const double *__restrict__ sums,
+                                                 const float *__restrict__ g, LossOut o) {
   const int l = blockIdx.y;
   const LossArgs &a = m.a[l];
   float *dvals = o.dvals[l];
@@ -325,8 +205,8 @@ SGNN_EXPORT int sgnn_loss_levels_fwd(const int64_t *levels, int n, const float *
   int gx = 1;
   for (int l = 0; l < n; ++l) gx = m.nblk[l] > gx ? m.nblk[l] : gx;
   hipStream_t s = (hipStream_t)stream;
-  SGNN_LAUNCH(k_loss_partial_multi, dim3(gx, n), dim3(256), 0, s, m, (double *)ws);
-  SGNN_LAUNCH(k_loss_finalize_multi, dim3(1), dim3(256), 0, s, (const double *)ws, m, sums, out2s, total, cur);
+  SGNN_LAUNCH(k_loss_partial, dim3(gx, n), dim3(256), 0, s, m, (double *)ws);
+  SGNN_LAUNCH(k_loss_finalize, dim3(1), dim3(256), 0, s, (const double *)ws, m, sums, out2s, total, cur);
   SGNN_CHECK_LAUNCH();
   return SGNN_OK;
 }
@@ -344,7 +224,7 @@ SGNN_EXPORT int sgnn_loss_levels_bwd(const int64_t *levels, int n, const float *
     o.dvals[l] = (float *)dvals[l];
     mmax = m.a[l].m > mmax ? m.a[l].m : mmax;
   }
-  SGNN_LAUNCH(k_loss_bwd_multi, dim3(sgnn_grid_for(mmax, 256, 2048), n), dim3(256), 0, (hipStream_t)stream, m, sums, g, o);
+  SGNN_LAUNCH(k_loss_bwd, dim3(sgnn_grid_for(mmax, 256, 2048), n), dim3(256), 0, (hipStream_t)stream, m, sums, g, o);
   SGNN_CHECK_LAUNCH();
   return SGNN_OK;
 }
@@ -489,49 +369,6 @@ SGNN_EXPORT int sgnn_loss_targets(const float *sdf, const uint8_t *known, const 
     const int64_t bricks = (int64_t)batch * ((d0 / 2 + 3) / 4) * ((d1 / 2 + 3) / 4) * ((d2 / 2 + 3) / 4);
     SGNN_LAUNCH(k_targets_coarse, dim3(sgnn_grid_for(bricks, 4, 8192)), dim3(256), 0, s, a);
   }
-  SGNN_CHECK_LAUNCH();
-  return SGNN_OK;
-}
-
-// ---------------------------------------------------------------------------
-// loss = sum_i coef[i] * out2s[i]  over the (bce, l1) pairs of all levels (torch/loss.py:160-199), per-level values
-// cur[l] = out2s[2l] + out2s[2l+1] for logging, and the matching gradient fan-out g2[i] = g * coef[i].
-// ---------------------------------------------------------------------------
-struct Coef10 {
-  float c[10];
-};
-
-__global__ void k_loss_combine(const float *__restrict__ out2s, Coef10 coef, int n, float *__restrict__ total,
-                               float *__restrict__ cur) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    float t = 0.f;
-    for (int i = 0; i < n; ++i)
-      if (coef.c[i] != 0.f) t += coef.c[i] * out2s[i];
-    *total = t;
-    for (int l = 0; 2 * l < n; ++l)
-      cur[l] = (coef.c[2 * l] != 0.f ? out2s[2 * l] : 0.f) + (coef.c[2 * l + 1] != 0.f ? out2s[2 * l + 1] : 0.f);
-  }
-}
-
-__global__ void k_loss_combine_bwd(const float *__restrict__ g, Coef10 coef, int n, float *__restrict__ g2) {
-  if (threadIdx.x < n && blockIdx.x == 0) g2[threadIdx.x] = g[0] * coef.c[threadIdx.x];
-}
-
-SGNN_EXPORT int sgnn_loss_combine(const float *out2s, const float *coef_host, int n, float *total, float *cur,
-                                  sgnn_stream_t stream) {
-  SGNN_CHECK_ARG(out2s && coef_host && total && cur && n >= 1 && n <= 10);
-  Coef10 c{};
-  for (int i = 0; i < n; ++i) c.c[i] = coef_host[i];
-  SGNN_LAUNCH(k_loss_combine, dim3(1), dim3(64), 0, (hipStream_t)stream, out2s, c, n, total, cur);
-  SGNN_CHECK_LAUNCH();
-  return SGNN_OK;
-}
-
-SGNN_EXPORT int sgnn_loss_combine_bwd(const float *g, const float *coef_host, int n, float *g2, sgnn_stream_t stream) {
-  SGNN_CHECK_ARG(g && coef_host && g2 && n >= 1 && n <= 10);
-  Coef10 c{};
-  for (int i = 0; i < n; ++i) c.c[i] = coef_host[i];
-  SGNN_LAUNCH(k_loss_combine_bwd, dim3(1), dim3(64), 0, (hipStream_t)stream, g, c, n, g2);
   SGNN_CHECK_LAUNCH();
   return SGNN_OK;
 }

@@ -84,18 +84,13 @@ __global__ __launch_bounds__(256) void k_iou_sparse(const int64_t *__restrict__ 
 template <typename T>
 __global__ __launch_bounds__(256) void k_iou_dense(const T *__restrict__ tgt, int64_t vol,
                                                   unsigned long long *__restrict__ counters) {
-  __shared__ unsigned int sh[256];
+  __shared__ unsigned int sh[1][256];
   const T *p = tgt + (int64_t)blockIdx.y * vol;
-  unsigned int c = 0;
+  unsigned int c[1] = {0};
   const int64_t stride = (int64_t)gridDim.x * 256;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < vol; i += stride) c += met_class<T>(p[i]) == 1;
-  sh[threadIdx.x] = c;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if (threadIdx.x < d) sh[threadIdx.x] += sh[threadIdx.x + d];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && sh[0]) atomicAdd(&counters[3 * blockIdx.y + 2], (unsigned long long)sh[0]);
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < vol; i += stride) c[0] += met_class<T>(p[i]) == 1;
+  sgnn_block_sum256(sh, c);
+  if (threadIdx.x == 0 && sh[0][0]) atomicAdd(&counters[3 * blockIdx.y + 2], (unsigned long long)sh[0][0]);
 }
 
 SGNN_EXPORT int sgnn_iou_counts(const int64_t *locs, const uint8_t *keep, const float *logits, int64_t lstride,
@@ -139,7 +134,7 @@ __global__ __launch_bounds__(256) void k_l1_tgtsurf_partial(const int64_t *__res
                                                            float truncation, float thresh, int nd,
                                                            double *__restrict__ partial) {
   __shared__ double sh[2][256];
-  double s = 0.0, c = 0.0;
+  double s[2] = {0.0, 0.0};   // sum, count
   const float fill = -truncation;
   if ((int)blockIdx.x < nd) {
     const int64_t total = (int64_t)g.nb * g.d0 * g.d1 * g.d2;
@@ -148,8 +143,8 @@ __global__ __launch_bounds__(256) void k_l1_tgtsurf_partial(const int64_t *__res
       const float t = tgt[i];
       if (!l1_on_surface(t, truncation, thresh)) continue;
       if (known && known[i] >= 2) continue;                      // loss.py:221-224, UNK_THRESH = 2
-      s += (double)fabsf(fill - t);
-      c += 1.0;
+      s[0] += (double)fabsf(fill - t);
+      s[1] += 1.0;
     }
   } else {
     const int64_t stride = (int64_t)(gridDim.x - nd) * 256;
@@ -160,40 +155,22 @@ __global__ __launch_bounds__(256) void k_l1_tgtsurf_partial(const int64_t *__res
       const float t = tgt[fl];
       if (!l1_on_surface(t, truncation, thresh)) continue;
       if (known && known[fl] >= 2) continue;
-      s += (double)fabsf(vals[r] - t) - (double)fabsf(fill - t);
+      s[0] += (double)fabsf(vals[r] - t) - (double)fabsf(fill - t);
     }
   }
-  sh[0][threadIdx.x] = s;
-  sh[1][threadIdx.x] = c;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if (threadIdx.x < d) {
-      sh[0][threadIdx.x] += sh[0][threadIdx.x + d];
-      sh[1][threadIdx.x] += sh[1][threadIdx.x + d];
-    }
-    __syncthreads();
-  }
+  sgnn_block_sum256(sh, s);
   if (threadIdx.x < 2) partial[2 * blockIdx.x + threadIdx.x] = sh[threadIdx.x][0];
 }
 
 __global__ __launch_bounds__(256) void k_l1_tgtsurf_final(const double *__restrict__ partial, int nblk,
                                                          double *__restrict__ out) {
   __shared__ double sh[2][256];
-  double s = 0.0, c = 0.0;
+  double s[2] = {0.0, 0.0};   // sum, count
   for (int b = threadIdx.x; b < nblk; b += 256) {
-    s += partial[2 * b];
-    c += partial[2 * b + 1];
+    s[0] += partial[2 * b];
+    s[1] += partial[2 * b + 1];
   }
-  sh[0][threadIdx.x] = s;
-  sh[1][threadIdx.x] = c;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if (threadIdx.x < d) {
-      sh[0][threadIdx.x] += sh[0][threadIdx.x + d];
-      sh[1][threadIdx.x] += sh[1][threadIdx.x + d];
-    }
-    __syncthreads();
-  }
+  sgnn_block_sum256(sh, s);
   if (threadIdx.x == 0) {
     out[0] = sh[0][0];
     out[1] = sh[1][0];

@@ -150,49 +150,15 @@ def compute_l1_predsurf_sparse_dense(sparse_pred_locs, sparse_pred_vals, dense_t
     return torch.mean(d)
 
 
-FUSED = True   # use the HIP level-loss kernels (sgnn_loss_level_*) for device tensors; False: torch ops below
-
-
-class _LevelLoss(torch.autograd.Function):
-    """(bce_mean, l1_mean) of one level through sgnn_loss_level_fwd/bwd (include/sgnn_hip.h)."""
-
-    @staticmethod
-    def forward(ctx, vals, locs, tgt_occ, tgt_sdf, weights, known, occ_col, sdf_col, use_log, mask_mode):
-        from . import _lib
-        from .scn.metadata import runtime
-        vals = vals.contiguous()
-        locs = locs.contiguous()
-        m, vstride = vals.shape
-        dims = tgt_sdf.shape[2:]
-        rt = runtime(vals.device)
-        sums = torch.empty(3, dtype=torch.float64, device=vals.device)
-        out2 = torch.empty(2, dtype=torch.float32, device=vals.device)
-        wsb = _lib.query('sgnn_loss_ws_bytes')
-        ws = rt.workspace(wsb)
-        m_cnt = info(locs).cnt     # capacity mode: live row count (device int64[1])
-        args = (_lib.ptr(locs), _lib.ptr(vals), vstride, occ_col, sdf_col, _lib.ptr(tgt_occ), _lib.ptr(tgt_sdf),
-                _lib.ptr(weights), _lib.ptr(known), int(dims[0]), int(dims[1]), int(dims[2]), m, int(use_log),
-                mask_mode, _lib.ptr(m_cnt))
-        _lib.call('sgnn_loss_level_fwd', *args, _lib.ptr(sums), _lib.ptr(out2), _lib.ptr(ws), wsb)
-        ctx.args = args
-        ctx.keep = (locs, vals, tgt_occ, tgt_sdf, weights, known, sums, m_cnt)
-        return out2
-
-    @staticmethod
-    def backward(ctx, g):
-        from . import _lib
-        locs, vals, tgt_occ, tgt_sdf, weights, known, sums, _m_cnt = ctx.keep
-        g = g.contiguous()
-        dvals = torch.empty_like(vals)
-        _lib.call('sgnn_loss_level_bwd', *ctx.args, _lib.ptr(sums), _lib.ptr(g), _lib.ptr(dvals))
-        return (dvals,) + (None,) * 9
+FUSED = True   # use the HIP loss kernels (sgnn_loss_levels_*, sgnn_loss_targets) for device tensors; False: torch ops
 
 
 class _TotalLoss(torch.autograd.Function):
-    """The whole hierarchical loss (loss.py:160-199) as one autograd node: per level sgnn_loss_level_fwd, then
-    sgnn_loss_combine for  sum_l weight_l * (bce_l + l1_l);  backward fans the incoming gradient out to the levels
-    (sgnn_loss_combine_bwd) and runs sgnn_loss_level_bwd per level.  `levels` = list of dicts (locs, tgt_occ, tgt_sdf,
-    weights, known, occ_col, sdf_col, mask_mode, coef (bce, l1)); vals_l are the differentiable inputs."""
+    """The hierarchical loss (loss.py:160-199) of up to five levels as one autograd node: sgnn_loss_levels_fwd gives
+    total = sum_l coef_l[0] * bce_l + coef_l[1] * l1_l  and the per-level values bce_l + l1_l (not differentiable, for
+    logging); backward is one sgnn_loss_levels_bwd (include/sgnn_hip.h).  `levels` = list of dicts (locs, tgt_occ,
+    tgt_sdf, weights, known, occ_col, sdf_col, mask_mode, coef (bce, l1)), see _fused_level; vals_l are the
+    differentiable inputs."""
 
     @staticmethod
     def forward(ctx, levels, use_log, *vals):
@@ -249,32 +215,45 @@ def _fusable(vals, *dense):
             all(d is None or (d.is_cuda and d.is_contiguous()) for d in dense))
 
 
+def _fused_level(locs, vals, tgt_occ, tgt_sdf, weights, known, use_loss_masking, coef):
+    """The _TotalLoss entry of one level, or None when the level is not fusable.  With tgt_occ: an occupancy + sdf
+    level (vals columns 0 and 1, masked by the UNK_ID targets); tgt_occ None: the final sdf-only level (masked by
+    `known`).  coef = the (bce, l1) weights of the level in the total."""
+    if tgt_occ is not None:
+        if not (_fusable(vals, tgt_occ, tgt_sdf, weights) and tgt_occ.dtype == torch.float32):
+            return None
+        return dict(locs=locs, tgt_occ=tgt_occ, tgt_sdf=tgt_sdf, weights=weights, known=None, occ_col=0, sdf_col=1,
+                    mask_mode=1 if use_loss_masking else 0, coef=coef)
+    if not (_fusable(vals, tgt_sdf, weights, known if use_loss_masking else None) and
+            (not use_loss_masking or known.dtype == torch.uint8)):
+        return None
+    return dict(locs=locs, tgt_occ=None, tgt_sdf=tgt_sdf, weights=weights, known=known if use_loss_masking else None,
+                occ_col=-1, sdf_col=0, mask_mode=2 if use_loss_masking else 0, coef=coef)
+
+
 def _compute_loss_fused(output_sdf, output_occs, target_for_sdf, target_for_occs, target_for_hier, loss_weights,
                         use_log_transform, use_loss_masking, known, weights):
-    """compute_loss through _TotalLoss when every active level is fusable; None otherwise."""
+    """compute_loss through one _TotalLoss when every active level is fusable; None otherwise."""
     levels, vals, slot = [], [], []
     for h in range(len(output_occs)):
         if len(output_occs[h][0]) == 0 or loss_weights[h] == 0:
             slot.append(None)
             continue
         locs, v = output_occs[h]
-        if not (_fusable(v, target_for_occs[h], target_for_hier[h], weights[h]) and
-                target_for_occs[h].dtype == torch.float32):
-            return None
         lw = float(loss_weights[h])
-        levels.append(dict(locs=locs, tgt_occ=target_for_occs[h], tgt_sdf=target_for_hier[h], weights=weights[h],
-                           known=None, occ_col=0, sdf_col=1, mask_mode=1 if use_loss_masking else 0, coef=(lw, lw)))
+        lv = _fused_level(locs, v, target_for_occs[h], target_for_hier[h], weights[h], None, use_loss_masking, (lw, lw))
+        if lv is None:
+            return None
+        levels.append(lv)
         vals.append(v)
         slot.append(len(levels) - 1)
     if len(output_sdf[0]) > 0 and loss_weights[-1] > 0:
-        v = output_sdf[1]
-        if not (_fusable(v, target_for_sdf, weights[-1], known if use_loss_masking else None) and
-                (not use_loss_masking or known.dtype == torch.uint8)):
+        lv = _fused_level(output_sdf[0], output_sdf[1], None, target_for_sdf, weights[-1], known, use_loss_masking,
+                          (0.0, float(loss_weights[-1])))
+        if lv is None:
             return None
-        levels.append(dict(locs=output_sdf[0], tgt_occ=None, tgt_sdf=target_for_sdf, weights=weights[-1],
-                           known=known if use_loss_masking else None, occ_col=-1, sdf_col=0,
-                           mask_mode=2 if use_loss_masking else 0, coef=(0.0, float(loss_weights[-1]))))
-        vals.append(v)
+        levels.append(lv)
+        vals.append(output_sdf[1])
         slot.append(len(levels) - 1)
     else:
         slot.append(None)
@@ -305,15 +284,16 @@ def compute_loss(output_sdf, output_occs, target_for_sdf, target_for_occs, targe
         weights = [None] * len(target_for_occs)
         if weight_missing_geo > 1:
             weights = compute_weights_missing_geo(weight_missing_geo, input_locs, target_for_occs, truncation)
+    # level by level: a fusable level is a one-level _TotalLoss (coefficient 1: its total is the level's value)
     for h in range(len(output_occs)):
         if len(output_occs[h][0]) == 0 or loss_weights[h] == 0:
             losses.append(-1)
             continue
         locs, vals = output_occs[h]
-        if _fusable(vals, target_for_occs[h], target_for_hier[h], weights[h]) and target_for_occs[h].dtype == torch.float32:
-            both = _LevelLoss.apply(vals, locs, target_for_occs[h], target_for_hier[h], weights[h], None, 0, 1,
-                                    use_log_transform, 1 if use_loss_masking else 0)
-            cur = both[0] + both[1]
+        lv = _fused_level(locs, vals, target_for_occs[h], target_for_hier[h], weights[h], None, use_loss_masking,
+                          (1.0, 1.0))
+        if lv is not None:
+            cur = _TotalLoss.apply([lv], bool(use_log_transform), vals)[0]
         else:
             l_occ = compute_bce_sparse_dense(locs, vals[:, 0], target_for_occs[h], weights[h], use_loss_masking)
             cur_known = None if not use_loss_masking else (target_for_occs[h] == UNK_ID) * UNK_THRESH
@@ -324,11 +304,9 @@ def compute_loss(output_sdf, output_occs, target_for_sdf, target_for_occs, targe
         losses.append(cur.detach())
     if len(output_sdf[0]) > 0 and loss_weights[-1] > 0:
         vals = output_sdf[1]
-        if _fusable(vals, target_for_sdf, weights[-1], known if use_loss_masking else None) and \
-                (not use_loss_masking or known.dtype == torch.uint8):
-            cur = _LevelLoss.apply(vals, output_sdf[0], None, target_for_sdf, weights[-1],
-                                   known if use_loss_masking else None, -1, 0, use_log_transform,
-                                   2 if use_loss_masking else 0)[1]
+        lv = _fused_level(output_sdf[0], vals, None, target_for_sdf, weights[-1], known, use_loss_masking, (0.0, 1.0))
+        if lv is not None:
+            cur = _TotalLoss.apply([lv], bool(use_log_transform), vals)[0]
         else:
             cur = compute_l1_predsurf_sparse_dense(output_sdf[0], vals, target_for_sdf, weights[-1],
                                                    use_log_transform, use_loss_masking, known)

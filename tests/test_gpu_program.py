@@ -95,7 +95,8 @@ def test_program_compiler_rejects_what_it_cannot_run():
 
 @pytest.mark.parametrize('masking,wgeo', [(True, 5.0), (False, 1.0), (True, 1.0)])
 def test_fused_level_loss_equals_torch_loss(masking, wgeo):
-    """sgnn_loss_level_fwd/bwd vs the torch-op restatement of torch/loss.py:58-157 (value and gradients)."""
+    """sgnn_loss_levels_fwd/bwd vs the torch-op restatement of torch/loss.py:58-157 (value and gradients); without
+    precomputed weights the (True, 5.0) case goes level by level, one n = 1 call each."""
     from sgnn_amd import loss as L
     torch.manual_seed(2)
     data = synth.make_batch(2, (16, 16, 16), cfg=9, occupancy=0.1)
@@ -128,6 +129,43 @@ def test_fused_level_loss_equals_torch_loss(masking, wgeo):
     assert np.allclose(lsa, lsb, rtol=1e-5, atol=1e-6)
     for x, y in zip(ga, gb):
         assert (x - y).abs().max().item() < 1e-6
+
+
+def test_one_level_calls_equal_the_all_levels_call_bit_for_bit():
+    """A level's value and gradient do not depend on which other levels share the sgnn_loss_levels_* call: the
+    level-by-level route of compute_loss (no precomputed weights; one n = 1 call per level, coefficient 1) gives the
+    same bits as the one all-levels call of the training step.  1500 sites on the finest and on the sdf level make
+    loss_blocks() two workgroups there, so the two-stage reduction and the per-level stride take part.  The totals
+    weight differently (sum lw*bce + lw*l1 slot by slot vs sum lw*(bce + l1)) and are held to 1e-6 relative."""
+    from sgnn_amd import loss as L
+    torch.manual_seed(3)
+    data = synth.make_batch(2, (16, 16, 16), cfg=9, occupancy=0.1)
+    dims = data['sdf'].shape[2:]
+    sites = lambda n, d: torch.stack([torch.randint(0, d[0], (n,)), torch.randint(0, d[1], (n,)),
+                                      torch.randint(0, d[2], (n,)), torch.randint(0, 2, (n,))], 1).cuda()
+    outs = [[sites(n, [v // f for v in dims]), torch.randn(n, 2).cuda()]
+            for f, n in ((8, 300), (4, 300), (2, 300), (1, 1500))]
+    sdf_locs, sdf_vals = outs[3][0], torch.randn(1500, 1).cuda()
+    lw = np.array([1, 0.5, 1, 1, 2], dtype=np.float32)
+    sdf, hier, known = data['sdf'].cuda(), [h.cuda() for h in data['hierarchy']], data['known'].cuda()
+    in_locs = data['input'][0].cuda()
+    (ts, occs, hiers), w = L.compute_targets_and_weights(sdf, hier, 4, 3.0, True, known, 5.0, in_locs)
+    res = []
+    for weights in (w, None):
+        vs = [o[1].clone().requires_grad_(True) for o in outs]
+        sv = sdf_vals.clone().requires_grad_(True)
+        loss, losses = L.compute_loss([sdf_locs, sv], [[o[0], v] for o, v in zip(outs, vs)], ts, occs, hiers, lw, 3.0,
+                                      True, 5.0, in_locs, True, known, weights=weights)
+        if weights is not None:
+            assert 'TotalLoss' in type(loss.grad_fn).__name__          # one all-levels launch each way
+        res.append((loss.detach(), [x.detach() for x in losses], torch.autograd.grad(loss, vs + [sv])))
+    (la, lsa, ga), (lb, lsb, gb) = res
+    assert len(lsa) == len(lsb) == 5
+    for h, (x, y) in enumerate(zip(lsa, lsb)):
+        assert torch.equal(x, y), (h, float(x), float(y))
+    for h, (x, y) in enumerate(zip(ga, gb)):
+        assert torch.equal(x, y), (h, (x - y).abs().max().item())
+    assert abs(la.item() - lb.item()) <= 1e-6 * abs(lb.item()), (la.item(), lb.item())
 
 
 def test_training_step_is_bitwise_reproducible():

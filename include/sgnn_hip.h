@@ -719,6 +719,22 @@ int sgnn_fuse_emit_rows(const float *sdf, int dx, int dy, float voxel_size, cons
 /* u8 known codes of the .knw file: sdf < -vs -> max(2, min(255, (int)(-sdf/vs) + 1)), sdf <= vs -> 1, else 0;
  * -inf -> 2 */
 int sgnn_fuse_known(const float *sdf, int64_t n, float voxel_size, uint8_t *known, sgnn_stream_t stream);
+/* Colour (rules in INTEGRATION.md section M).  Colour frames are one (nframes, h, w, 4) u8 stack, memory order R, G, B,
+ * A, on the pixel grid of the depth stack; A != 0 = the pixel has a colour.  The colour state of a volume is one
+ * (dz, dy, dx, 4) u16 array, 8-byte aligned: R, G, B in 8.8 fixed point and the colour weight 0..255, zero at the start.
+ * out = raw (nframes, h_raw, w_raw, channels = 3 | 4) u8 resampled to (h, w) by sgnn_fuse_depth_raw's nearest index;
+ * A = 255 for 3 channels, (a != 0) ? 255 : 0 for 4 */
+int sgnn_fusecol_pack(const uint8_t *raw, int nframes, int h_raw, int w_raw, int channels, int h, int w, uint8_t *out,
+                      sgnn_stream_t stream);
+/* sgnn_fuse_integrate that also folds rgba into color: same geometry result bit for bit; a sample that updates the
+ * geometry, was not clamped on the free-space side and whose pixel has A != 0 updates the voxel's colour */
+int sgnn_fusecol_integrate(float *sdf, uint8_t *weight, int32_t *free_ctr, uint16_t *color, int dx, int dy, int dz,
+                           const float *depth, const uint8_t *rgba, int h, int w, const sgnn_fuse_frame *frames,
+                           int nframes, int chunk, float voxel_size, float depth_min, float depth_max,
+                           const float *obb, sgnn_stream_t stream);
+/* rgb (n, 3) u8 = (q + 128) >> 8 where the colour weight is positive, else 0; wc (n) u8 = the colour weight, or NULL.
+ * rgb and wc 4-byte aligned */
+int sgnn_fusecol_export(const uint16_t *color, int64_t n, uint8_t *rgb, uint8_t *wc, sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Training chunks cut from a fused scan pair (sgnn_amd.chunks; rules in INTEGRATION.md "Training chunks"): window

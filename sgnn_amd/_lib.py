@@ -126,6 +126,10 @@ PROTOTYPES = {
     'sgnn_fuse_emit_block': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     'sgnn_fuse_emit_rows': (c_i32, [c_vp, c_i32, c_i32, c_f32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     'sgnn_fuse_known': (c_i32, [c_vp, c_i64, c_f32, c_vp, c_vp]),
+    'sgnn_fusecol_pack': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    'sgnn_fusecol_integrate': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32,
+                                       c_i32, c_f32, c_f32, c_f32, c_vp, c_vp]),
+    'sgnn_fusecol_export': (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     'sgnn_chunk_score': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_i32, c_i32, c_i32, c_i32, c_i32,
                                  c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     'sgnn_chunk_flag': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_vp,

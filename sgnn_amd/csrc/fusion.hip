@@ -5,9 +5,12 @@
 //
 // Kernels:
 //   k_fuse_depth_raw      uint16 frames -> metric fp32 depth (nearest-index resampling, range test)     1 thread / pixel
+//   k_fusecol_pack        uint8 RGB / RGBA frames -> RGBA frames on the depth frames' pixel grid        1 thread / pixel
 //   k_fuse_bilateral      edge-preserving filter of the metric frames                                   1 thread / pixel
 //   k_fuse_integrate      the hot path: every voxel folds a chunk of frames in input order, its (sdf, weight, free
-//                         counter) in registers; state is read and written once per chunk
+//                         counter) in registers; state is read and written once per chunk.  <COLOR = true> also
+//                         folds the frames' colour into an 8-byte (R, G, B, weight) record per voxel
+//   k_fusecol_export      colour records -> uint8 RGB (the colour volume marching cubes takes) and colour weights
 //   k_fuse_flag           |sdf| <= keep (the sparse file filter), optionally |sdf/vs| < truncation and z < max_z
 //   k_fuse_emit_block     kept voxels -> (x,y,z) u32 + metric sdf f32, the .sdf block layout
 //   k_fuse_emit_rows      kept voxels -> [z,y,x,0] int64 rows + sdf/vs features (the collated scene input)
@@ -15,7 +18,7 @@
 // Compaction between flag and emit is sgnn_compact_mask (stable: raster order, x fastest).
 //
 // Built with -ffp-contract=off (Makefile): every product and sum below is rounded on its own, so the fp32
-// restatement in the tests reproduces sdf, weight and free counter bit for bit.
+// restatement in the tests reproduces sdf, weight, free counter and colour record bit for bit.
 #include <math.h>
 #include "common.h"
 
@@ -66,6 +69,26 @@ __global__ __launch_bounds__(256) void k_fuse_depth_raw(const uint16_t *__restri
   }
 }
 
+// the resampling of k_fuse_depth_raw for colour frames of `ch` = 3 or 4 bytes per pixel: out = R | G << 8 | B << 16 |
+// A << 24 (memory order R, G, B, A), A = 255 for 3 channels and (a != 0) ? 255 : 0 for 4
+__global__ __launch_bounds__(256) void k_fusecol_pack(const uint8_t *__restrict__ raw, int64_t npix, int hr, int wr,
+                                                     int ch, int h, int w, uint32_t *__restrict__ out) {
+  const float fx = __fdiv_rn((float)(wr - 1), (float)(w - 1));
+  const float fy = __fdiv_rn((float)(hr - 1), (float)(h - 1));
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < npix; p += stride) {
+    const int64_t f = p / ((int64_t)h * w);
+    const int r = (int)(p - f * h * w);
+    const int j = r / w, i = r - j * w;
+    int x = (int)roundf((float)i * fx), y = (int)roundf((float)j * fy);
+    x = min(x, wr - 1);
+    y = min(y, hr - 1);
+    const uint8_t *s = raw + ((f * hr + y) * wr + x) * ch;
+    const uint32_t a = (ch == 3 || s[3] != 0) ? 255u : 0u;
+    out[p] = (uint32_t)s[0] | (uint32_t)s[1] << 8 | (uint32_t)s[2] << 16 | a << 24;
+  }
+}
+
 // output = sum w * d / sum w over finite neighbours within `radius`, w = exp(-(dx^2+dy^2) / (2 sd^2)) *
 // exp(-(d - c)^2 / (2 sr^2)); -inf where the centre is not finite or the weights sum to 0
 __global__ __launch_bounds__(256) void k_fuse_bilateral(const float *__restrict__ in, int64_t npix, int h, int w,
@@ -102,9 +125,16 @@ __global__ __launch_bounds__(256) void k_fuse_bilateral(const float *__restrict_
 // Frames f0 .. f1-1 into the volume.  Workgroup = one 64x4x1 brick; the frame loop is workgroup-uniform (the table
 // is read with scalar loads, the brick test needs no lane), so a frame whose box misses the brick costs a few
 // scalar instructions and a brick that no frame of the chunk touches neither loads nor stores its state.
+//
+// COLOR: `color` holds one uint2 per voxel, four 16-bit fields R, G, B (8.8 fixed point) and the colour weight; `rgba`
+// is the colour stack, 4 bytes per pixel on the depth stack's pixel grid, so a pixel has the same byte offset in
+// both.  A sample that was not clamped on the free-space side and whose pixel has A != 0 folds its colour with the
+// weight of the geometry update.  The colour fetch sits behind all the tests: only lanes that will use it ask for it.
+template <bool COLOR>
 __global__ __launch_bounds__(256) void k_fuse_integrate(float *__restrict__ sdf, uint8_t *__restrict__ weight,
-                                                       int32_t *__restrict__ freec, int dx, int dy,
-                                                       const float *__restrict__ depth, int h, int w,
+                                                       int32_t *__restrict__ freec, uint2 *__restrict__ color,
+                                                       int dx, int dy, const float *__restrict__ depth,
+                                                       const uint8_t *__restrict__ rgba, int h, int w,
                                                        const sgnn_fuse_frame *__restrict__ fr, int f0, int f1,
                                                        float vs, float dmin, float dmax, FuseObb obb) {
   const int x0 = blockIdx.x * BRICK_X, y0 = blockIdx.y * BRICK_Y, k = blockIdx.z;
@@ -119,10 +149,19 @@ __global__ __launch_bounds__(256) void k_fuse_integrate(float *__restrict__ sdf,
   float s = -INFINITY;
   int wt = 0;
   int32_t fc = 0;
+  float q[3] = {0.f, 0.f, 0.f};                                            // integer-valued: what is stored and reloaded
+  int wc = 0;
   if (inside) {
     s = sdf[v];
     wt = weight[v];
     fc = freec[v];
+    if constexpr (COLOR) {
+      const uint2 c = color[v];
+      q[0] = (float)(c.x & 0xFFFFu);
+      q[1] = (float)(c.x >> 16);
+      q[2] = (float)(c.y & 0xFFFFu);
+      wc = (int)(c.y >> 16);
+    }
   }
   const float fi = (float)i, fj = (float)j, fk = (float)k;
   const bool eligible = inside && (!obb.on || obb_contains(obb, fi, fj, fk));
@@ -148,20 +187,73 @@ __global__ __launch_bounds__(256) void k_fuse_integrate(float *__restrict__ sdf,
     const float d = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0));
     if (!(on_image && d >= dmin && d <= dmax)) continue;
     if (pz < d) ++fc;                                                     // voxel in front of the observation
-    float sd = d - pz;
+    const float sd0 = d - pz;
     const float trunc = trunc0 + d * vs;
-    if (!(sd > -trunc)) continue;
-    sd = sd >= 0.f ? fminf(trunc, sd) : fmaxf(-trunc, sd);
+    if (!(sd0 > -trunc)) continue;
+    const float sd = sd0 >= 0.f ? fminf(trunc, sd0) : fmaxf(-trunc, sd0);
     const float z01 = __fdiv_rn(d - 0.4f, 4.0f - 0.4f);                 // the weight ramp is fixed to 0.4 .. 4.0 m
     const float wu = fmaxf(4.5f * (1.0f - z01), 1.0f);
     if (s == -INFINITY) s = sd;
     else s = __fdiv_rn(s * (float)wt + sd * wu, (float)wt + wu);
     wt = min(wt + (int)wu, 255);
+    if constexpr (COLOR) {
+      if (!(sd0 < trunc)) continue;                                       // free space gets no colour
+      const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<uint8_t *>(rgba + F.offset * 4), 0, (int)frame_bytes, 0x00020000);
+      const uint32_t px4 = __builtin_amdgcn_raw_buffer_load_b32(rc, off, 0, 0);
+      if ((px4 >> 24) == 0u) continue;                                    // A == 0: the pixel has no colour
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float ci = (float)(((px4 >> (8 * c)) & 0xFFu) * 256u);
+        if (wc == 0) q[c] = ci;
+        else q[c] = roundf(__fdiv_rn(q[c] * (float)wc + ci * wu, (float)wc + wu));
+      }
+      wc = min(wc + (int)wu, 255);
+    }
   }
   if (inside) {
     sdf[v] = s;
     weight[v] = (uint8_t)wt;
     freec[v] = fc;
+    if constexpr (COLOR) {
+      color[v] = make_uint2((uint32_t)q[0] | (uint32_t)q[1] << 16, (uint32_t)q[2] | (uint32_t)wc << 16);
+    }
+  }
+}
+
+// c8 = (q + 128) >> 8 where the colour weight is positive, else 0.  One thread takes four voxels: 32 bytes in, 12 + 4 out.
+__global__ __launch_bounds__(256) void k_fusecol_export(const uint2 *__restrict__ color, int64_t n,
+                                                       uint8_t *__restrict__ rgb, uint8_t *__restrict__ wcout) {
+  const int64_t groups = (n + 3) / 4;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += stride) {
+    const int64_t v0 = 4 * g;
+    const int m = (int)(n - v0 < 4 ? n - v0 : 4);
+    uint8_t o[12];
+    uint8_t wq[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const uint2 c = t < m ? color[v0 + t] : make_uint2(0u, 0u);
+      const uint32_t wc = c.y >> 16;
+      wq[t] = (uint8_t)wc;
+      o[3 * t] = wc ? (uint8_t)(((c.x & 0xFFFFu) + 128u) >> 8) : 0;
+      o[3 * t + 1] = wc ? (uint8_t)(((c.x >> 16) + 128u) >> 8) : 0;
+      o[3 * t + 2] = wc ? (uint8_t)(((c.y & 0xFFFFu) + 128u) >> 8) : 0;
+    }
+    if (m == 4) {                                                         // rgb + 12 g and wcout + 4 g are 4-byte aligned
+#pragma unroll
+      for (int t = 0; t < 3; ++t) {
+        reinterpret_cast<uint32_t *>(rgb + 3 * v0)[t] = (uint32_t)o[4 * t] | (uint32_t)o[4 * t + 1] << 8 |
+                                                        (uint32_t)o[4 * t + 2] << 16 | (uint32_t)o[4 * t + 3] << 24;
+      }
+      if (wcout) {
+        *reinterpret_cast<uint32_t *>(wcout + v0) =
+            (uint32_t)wq[0] | (uint32_t)wq[1] << 8 | (uint32_t)wq[2] << 16 | (uint32_t)wq[3] << 24;
+      }
+    } else {
+      for (int t = 0; t < 3 * m; ++t) rgb[3 * v0 + t] = o[t];
+      for (int t = 0; t < m && wcout; ++t) wcout[v0 + t] = wq[t];
+    }
   }
 }
 
@@ -245,14 +337,28 @@ SGNN_EXPORT int sgnn_fuse_bilateral(const float *in, int nframes, int h, int w, 
   return SGNN_OK;
 }
 
-SGNN_EXPORT int sgnn_fuse_integrate(float *sdf, uint8_t *weight, int32_t *free_ctr, int dx, int dy, int dz,
-                                    const float *depth, int h, int w, const sgnn_fuse_frame *frames, int nframes,
-                                    int chunk, float voxel_size, float depth_min, float depth_max, const float *obb,
-                                    sgnn_stream_t stream) {
+SGNN_EXPORT int sgnn_fusecol_pack(const uint8_t *raw, int nframes, int h_raw, int w_raw, int channels, int h, int w,
+                                  uint8_t *out, sgnn_stream_t stream) {
+  SGNN_CHECK_ARG(nframes >= 0 && h_raw >= 2 && w_raw >= 2 && h >= 2 && w >= 2 && (channels == 3 || channels == 4));
+  if (nframes == 0) return SGNN_OK;
+  SGNN_CHECK_ARG(raw && out && raw != out && ((uintptr_t)out & 3) == 0);
+  const int64_t npix = (int64_t)nframes * h * w;
+  SGNN_LAUNCH(k_fusecol_pack, dim3(sgnn_grid_for(npix, 256, 8192)), dim3(256), 0, (hipStream_t)stream, raw, npix, h_raw,
+              w_raw, channels, h, w, reinterpret_cast<uint32_t *>(out));
+  SGNN_CHECK_LAUNCH();
+  return SGNN_OK;
+}
+
+// the one host side of both integrate entry points; color / rgba NULL = the depth-only instantiation
+static int fuse_integrate(float *sdf, uint8_t *weight, int32_t *free_ctr, uint16_t *color, int dx, int dy, int dz,
+                          const float *depth, const uint8_t *rgba, int h, int w, const sgnn_fuse_frame *frames,
+                          int nframes, int chunk, float voxel_size, float depth_min, float depth_max, const float *obb,
+                          sgnn_stream_t stream) {
   SGNN_CHECK_ARG(dx >= 1 && dy >= 1 && dz >= 1 && dz <= 65535 && h >= 1 && w >= 1 && nframes >= 0);
   SGNN_CHECK_ARG((int64_t)h * w <= ((int64_t)1 << 29));    // one frame's byte range fits a buffer resource
   if (nframes == 0) return SGNN_OK;
   SGNN_CHECK_ARG(sdf && weight && free_ctr && depth && frames && voxel_size > 0.f);
+  SGNN_CHECK_ARG((color != nullptr) == (rgba != nullptr) && ((uintptr_t)color & 7) == 0 && ((uintptr_t)rgba & 3) == 0);
   FuseObb o{};
   if (obb) {
     o.on = 1;
@@ -266,10 +372,43 @@ SGNN_EXPORT int sgnn_fuse_integrate(float *sdf, uint8_t *weight, int32_t *free_c
   const dim3 grid((dx + BRICK_X - 1) / BRICK_X, (dy + BRICK_Y - 1) / BRICK_Y, dz);
   for (int f0 = 0; f0 < nframes; f0 += chunk) {
     const int f1 = f0 + chunk < nframes ? f0 + chunk : nframes;
-    SGNN_LAUNCH(k_fuse_integrate, grid, dim3(256), 0, (hipStream_t)stream, sdf, weight, free_ctr, dx, dy, depth, h, w,
-                frames, f0, f1, voxel_size, depth_min, depth_max, o);
+    if (color) {
+      SGNN_LAUNCH(k_fuse_integrate<true>, grid, dim3(256), 0, (hipStream_t)stream, sdf, weight, free_ctr,
+                  reinterpret_cast<uint2 *>(color), dx, dy, depth, rgba, h, w, frames, f0, f1, voxel_size, depth_min,
+                  depth_max, o);
+    } else {
+      SGNN_LAUNCH(k_fuse_integrate<false>, grid, dim3(256), 0, (hipStream_t)stream, sdf, weight, free_ctr,
+                  (uint2 *)nullptr, dx, dy, depth, rgba, h, w, frames, f0, f1, voxel_size, depth_min, depth_max, o);
+    }
     SGNN_CHECK_LAUNCH();
   }
+  return SGNN_OK;
+}
+
+SGNN_EXPORT int sgnn_fuse_integrate(float *sdf, uint8_t *weight, int32_t *free_ctr, int dx, int dy, int dz,
+                                    const float *depth, int h, int w, const sgnn_fuse_frame *frames, int nframes,
+                                    int chunk, float voxel_size, float depth_min, float depth_max, const float *obb,
+                                    sgnn_stream_t stream) {
+  return fuse_integrate(sdf, weight, free_ctr, nullptr, dx, dy, dz, depth, nullptr, h, w, frames, nframes, chunk,
+                        voxel_size, depth_min, depth_max, obb, stream);
+}
+
+SGNN_EXPORT int sgnn_fusecol_integrate(float *sdf, uint8_t *weight, int32_t *free_ctr, uint16_t *color, int dx, int dy,
+                                       int dz, const float *depth, const uint8_t *rgba, int h, int w,
+                                       const sgnn_fuse_frame *frames, int nframes, int chunk, float voxel_size,
+                                       float depth_min, float depth_max, const float *obb, sgnn_stream_t stream) {
+  if (nframes > 0) SGNN_CHECK_ARG(color && rgba);
+  return fuse_integrate(sdf, weight, free_ctr, color, dx, dy, dz, depth, rgba, h, w, frames, nframes, chunk,
+                        voxel_size, depth_min, depth_max, obb, stream);
+}
+
+SGNN_EXPORT int sgnn_fusecol_export(const uint16_t *color, int64_t n, uint8_t *rgb, uint8_t *wc, sgnn_stream_t stream) {
+  SGNN_CHECK_ARG(n >= 0);
+  if (n == 0) return SGNN_OK;
+  SGNN_CHECK_ARG(color && rgb && ((uintptr_t)color & 7) == 0 && ((uintptr_t)rgb & 3) == 0 && ((uintptr_t)wc & 3) == 0);
+  SGNN_LAUNCH(k_fusecol_export, dim3(sgnn_grid_for((n + 3) / 4, 256, 8192)), dim3(256), 0, (hipStream_t)stream,
+              reinterpret_cast<const uint2 *>(color), n, rgb, wc);
+  SGNN_CHECK_LAUNCH();
   return SGNN_OK;
 }
 

@@ -9,6 +9,7 @@ independent NumPy restatement of the tests (tests/fusion_ref.py) both follow.
     depth, K = raw_depth_to_metric(raw_u16, 1000.0, (240, 320), intrinsics=K_raw)
     vol = TSDFVolume((dx, dy, dz), 0.02, world2grid)
     vol.integrate(bilateral(depth), K, cam2world)           # all frames in one call, no per-frame host loop
+    # with TSDFVolume(..., color=True): vol.integrate(..., color=pack_color(rgb, (240, 320))); vol.colors()
     vol.save('scene.sdf')                                    # + scene.knw, readable by data.load_scene / loaders
     sample = scan_sample(vol)                                # or straight to a model input on the device
 
@@ -79,6 +80,24 @@ def raw_depth_to_metric(raw_u16, depth_shift, out_hw, min_depth=0.1, max_depth=1
     return (out[0] if single else out), k
 
 
+def pack_color(rgb, out_hw=None):
+    """uint8 colour frames (h_raw, w_raw, c) or (F, h_raw, w_raw, c), c = 3 (R, G, B) or 4 (R, G, B, A), numpy or
+    torch, host or device -> the (F, h, w, 4) uint8 device stack TSDFVolume.integrate(color=) takes, resampled to
+    out_hw = (h, w) by raw_depth_to_metric's nearest-index rule (None: the frames' own size).  A = 255 where the pixel
+    has a colour (every pixel of 3-channel input, a != 0 of 4-channel input), else 0."""
+    dev = _device(rgb.device if torch.is_tensor(rgb) and rgb.is_cuda else None)
+    raw = _to_device(rgb if torch.is_tensor(rgb) else _host(rgb, np.uint8), torch.uint8, dev)
+    if raw.dim() == 3:
+        raw = raw[None]
+    if raw.dim() != 4 or int(raw.shape[3]) not in (3, 4):
+        raise ValueError('colour frames must be (F, h, w, 3|4) or (h, w, 3|4), got %s' % (tuple(raw.shape),))
+    nf, hr, wr, ch = (int(v) for v in raw.shape)
+    h, w = (hr, wr) if out_hw is None else (int(v) for v in out_hw)
+    out = torch.empty((nf, h, w, 4), dtype=torch.uint8, device=dev)
+    _lib.call('sgnn_fusecol_pack', raw.data_ptr(), nf, hr, wr, ch, h, w, out.data_ptr())
+    return out
+
+
 def bilateral(depth, sigma_d=2.0, sigma_r=0.1):
     """Bilateral filter of (h, w) or (F, h, w) metric depth (CameraUtil.h:25-63); -inf stays -inf."""
     dev = _device(depth.device if torch.is_tensor(depth) and depth.is_cuda else None)
@@ -88,6 +107,15 @@ def bilateral(depth, sigma_d=2.0, sigma_r=0.1):
     _lib.call('sgnn_fuse_bilateral', d3.data_ptr(), int(d3.shape[0]), int(d3.shape[1]), int(d3.shape[2]),
               float(sigma_d), float(sigma_r), out.data_ptr())
     return out[0] if d.dim() == 2 else out
+
+
+def color_stack(color, dev):
+    """What integrate(color=) was given -> the (F, h, w, 4) uint8 stack on dev: a stack that is already there is
+    used as it is (the kernel only asks whether A != 0), anything else goes through pack_color at its own size."""
+    if torch.is_tensor(color) and color.is_cuda and color.dtype == torch.uint8 and color.dim() == 4 and \
+            int(color.shape[3]) == 4 and color.device == dev:
+        return color.contiguous()
+    return pack_color(color.to(dev) if torch.is_tensor(color) else color)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -150,9 +178,11 @@ class TSDFVolume(object):
 
     dims_xyz: (dx, dy, dz) voxels; voxel_size in metres; world2grid: 4x4 (world metres -> voxel coordinates);
     depth_min / depth_max: the depths an observation may have; obb: optional (a, e0, e1, e2) in voxel
-    coordinates, voxels outside it are never updated."""
+    coordinates, voxels outside it are never updated; color: also keep a colour per voxel,
+    8 more bytes per voxel, fed by integrate(color=) and read with colors()."""
 
-    def __init__(self, dims_xyz, voxel_size, world2grid, depth_min=0.4, depth_max=4.0, obb=None, device=None):
+    def __init__(self, dims_xyz, voxel_size, world2grid, depth_min=0.4, depth_max=4.0, obb=None, device=None,
+                 color=False):
         self.device = _device(device)
         self.dims_xyz = tuple(int(d) for d in dims_xyz)
         dx, dy, dz = self.dims_xyz
@@ -165,6 +195,9 @@ class TSDFVolume(object):
         self._sdf = torch.full((dz, dy, dx), -float('inf'), dtype=torch.float32, device=self.device)
         self._weight = torch.zeros((dz, dy, dx), dtype=torch.uint8, device=self.device)
         self._free = torch.zeros((dz, dy, dx), dtype=torch.int32, device=self.device)
+        # R, G, B in 8.8 fixed point and the colour weight, or None; held as int16 (torch fills and copies that type
+        # everywhere), handed out as uint16
+        self._color = torch.zeros((dz, dy, dx, 4), dtype=torch.int16, device=self.device) if color else None
 
     @property
     def dims_zyx(self):
@@ -191,14 +224,22 @@ class TSDFVolume(object):
         t['offset'] = np.arange(nf, dtype=np.int64) * (int(hw[0]) * int(hw[1]))
         return t
 
-    def integrate(self, depth, intrinsics, cam2world, chunk=None):
+    def integrate(self, depth, intrinsics, cam2world, chunk=None, color=None):
         """Fuse F frames in order.  depth (F, h, w) metres (-inf = invalid), intrinsics (F, 4) fx, fy, cx, cy,
         cam2world (F, 4, 4); torch tensors (host or device) or numpy arrays.  chunk: frames per launch (the result
-        does not depend on it; None: DEFAULT_CHUNK)."""
+        does not depend on it; None: DEFAULT_CHUNK).  color: the frames' colours for a volume built with color=True,
+        a pack_color() stack or raw (F, h, w, 3|4) uint8 frames of the depth frames' size; None leaves the colours
+        as they are."""
         d = _to_device(depth, torch.float32, self.device)
         if d.dim() == 2:
             d = d[None]
         nf, h, w = (int(v) for v in d.shape)
+        if color is not None:
+            if self._color is None:
+                raise ValueError('colour frames for a volume built without color=True')
+            color = color_stack(color, self.device)
+            if tuple(color.shape) != (nf, h, w, 4):
+                raise ValueError('colour frames %s for depth frames %s' % (tuple(color.shape[:3]), (nf, h, w)))
         table = self.frame_table(intrinsics, cam2world, (h, w))
         if table.shape[0] != nf:
             raise ValueError('%d depth frames for %d poses' % (nf, table.shape[0]))
@@ -207,9 +248,14 @@ class TSDFVolume(object):
         dev_table = torch.from_numpy(table.view(np.uint8)).to(self.device)
         dx, dy, dz = self.dims_xyz
         obb = None if self.obb is None else self.obb.ctypes.data
-        _lib.call('sgnn_fuse_integrate', self._sdf.data_ptr(), self._weight.data_ptr(), self._free.data_ptr(), dx, dy,
-                  dz, d.data_ptr(), h, w, dev_table.data_ptr(), nf, int(DEFAULT_CHUNK if chunk is None else chunk),
-                  float(self.voxel_size), float(self.depth_min), float(self.depth_max), obb)
+        tail = (h, w, dev_table.data_ptr(), nf, int(DEFAULT_CHUNK if chunk is None else chunk),
+                float(self.voxel_size), float(self.depth_min), float(self.depth_max), obb)
+        if color is None:
+            _lib.call('sgnn_fuse_integrate', self._sdf.data_ptr(), self._weight.data_ptr(), self._free.data_ptr(), dx,
+                      dy, dz, d.data_ptr(), *tail)
+        else:
+            _lib.call('sgnn_fusecol_integrate', self._sdf.data_ptr(), self._weight.data_ptr(), self._free.data_ptr(),
+                      self._color.data_ptr(), dx, dy, dz, d.data_ptr(), color.data_ptr(), *tail)
         return self
 
     def sdf(self):
@@ -221,11 +267,41 @@ class TSDFVolume(object):
     def free_count(self):
         return self._free
 
+    def color_state(self):
+        """(dz, dy, dx, 4) uint16: R, G, B in 8.8 fixed point and the colour weight; None without color=True."""
+        return None if self._color is None else self._color.view(torch.uint16)
+
+    def _export_color(self, want_weight):
+        if self._color is None:
+            raise ValueError('the volume was built without color=True')
+        dx, dy, dz = self.dims_xyz
+        rgb = torch.empty((dz, dy, dx, 3), dtype=torch.uint8, device=self.device)
+        wc = torch.empty((dz, dy, dx), dtype=torch.uint8, device=self.device) if want_weight else None
+        _lib.call('sgnn_fusecol_export', self._color.data_ptr(), dx * dy * dz, rgb.data_ptr(), _lib.ptr(wc))
+        return rgb, wc
+
+    def color_weight(self):
+        """(dz, dy, dx) uint8: the weight behind each voxel's colour, 0 = no colour."""
+        return self._export_color(True)[1]
+
+    def colors(self, dims_zyx=None):
+        """(dz, dy, dx, 3) uint8 R, G, B, black where a voxel has no colour: the colour volume that
+        marching_cubes.run_marching_cubes takes next to sdf().  dims_zyx: zero-padded or cropped to those dims (the
+        padded dense volume of a prediction)."""
+        rgb = self._export_color(False)[0]
+        if dims_zyx is None or tuple(int(v) for v in dims_zyx) == tuple(rgb.shape[:3]):
+            return rgb
+        out = torch.zeros(tuple(int(v) for v in dims_zyx) + (3,), dtype=torch.uint8, device=self.device)
+        z, y, x = (min(int(a), int(b)) for a, b in zip(dims_zyx, rgb.shape[:3]))
+        out[:z, :y, :x] = rgb[:z, :y, :x]
+        return out
+
     def copy(self):
         """An independent snapshot (the input half of a subset / all-frames pair, Fuser.cpp:71-100)."""
         c = TSDFVolume.__new__(TSDFVolume)
         c.__dict__.update(self.__dict__)
         c._sdf, c._weight, c._free = self._sdf.clone(), self._weight.clone(), self._free.clone()
+        c._color = None if self._color is None else self._color.clone()
         return c
 
     def _compact(self, keep_abs, truncation=0.0, max_z=1 << 40):
@@ -306,11 +382,14 @@ class TSDFPyramid(object):
     def __getitem__(self, k):
         return self.volumes[k]
 
-    def integrate(self, depth, intrinsics, cam2world, chunk=None):
-        """TSDFVolume.integrate on every level (the depth stack is moved to the device once)."""
+    def integrate(self, depth, intrinsics, cam2world, chunk=None, color=None):
+        """TSDFVolume.integrate on every level (the depth and colour stacks are moved to the device, and the colour
+        stack packed, once)."""
         d = _to_device(depth, torch.float32, self.volumes[0].device)
+        if color is not None:
+            color = color_stack(color, self.volumes[0].device)
         for v in self.volumes:
-            v.integrate(d, intrinsics, cam2world, chunk)
+            v.integrate(d, intrinsics, cam2world, chunk, color)
         return self
 
     def copy(self):

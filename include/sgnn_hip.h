@@ -484,6 +484,10 @@ int sgnn_linear_bwd(const float *x, const float *dy, int64_t n, int cin, const f
  * out2s (2n floats), total, cur (n floats): device; g: device float = d loss / d total; dvals: HOST array of n device
  * pointers, (m_l, vstride_l) floats each.  The fp64 two-stage reduction has a fixed order per level, which depends on
  * that level's m alone: the same level gives the same bits whichever other levels share the call.
+ * Contracts: every row of locs, rows past the live count included, must lie inside its (B, d0, d1, d2) volume (the
+ * kernels gather without a bounds check) and locs must be 16-byte aligned (it is read with 16-byte loads); dvals rows
+ * past the live count min(max(*m_dev, 0), m) are left unwritten, rows below it are written in every column (+0 for a
+ * row that is not kept and for the columns other than occ_col / sdf_col).
  * ------------------------------------------------------------------------- */
 int64_t sgnn_loss_multi_ws_bytes(void);
 int sgnn_loss_levels_fwd(const int64_t *levels, int n, const float *coef_host, double *sums, float *out2s, float *total,
@@ -496,7 +500,9 @@ int sgnn_loss_levels_bwd(const int64_t *levels, int n, const float *coef_host, c
  * where known >= 2 (masking); w_last = weight_missing_geo off the input sites, 1 on them; and for the ncoarse (<= 3)
  * coarser levels, listed from the second finest downwards in the host pointer arrays hier_in / occ / w / hier:
  * occ = 2x2x2 max-pool of the level above, w = that level's w[::2,::2,::2], hier = clamp(hier_in).  w_last NULL: no
- * weights.  input_locs = the (n_locs, 4) int64 [z,y,x,b] input sites.  Dimensions must be divisible by 2^ncoarse. */
+ * weights.  input_locs = the (n_locs, 4) int64 [z,y,x,b] input sites, of which the first min(max(*n_locs_dev, 0), n_locs)
+ * count (n_locs_dev NULL: all); a site outside the (batch, d0, d1, d2) volume is skipped.  The clamp keeps NaN, like
+ * torch.clamp_.  Dimensions must be divisible by 2^ncoarse; every output must be 8-byte aligned. */
 int sgnn_loss_targets(const float *sdf, const uint8_t *known, const int64_t *input_locs, int64_t n_locs,
                       const int64_t *n_locs_dev, int batch,
                       int d0, int d1, int d2, float trunc, int masking, float weight_missing_geo, int ncoarse,

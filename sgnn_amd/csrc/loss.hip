@@ -238,13 +238,17 @@ SGNN_EXPORT int sgnn_loss_levels_bwd(const int64_t *levels, int n, const float *
 //   coarse : occ[h] = 2x2x2 max of occ[h+1]; w[h] = w[h+1][::2,::2,::2]; hier[h] = clamp(hierarchy[h]) for the (up to
 //            three) coarser levels, one wave per 8^3 fine voxels (4x4x4 voxels of level L-2), maxima by lane shuffles.
 // ---------------------------------------------------------------------------
+// clamp to +-trunc like torch.clamp_ / the reference's masked assignments: -inf -> -trunc, +inf -> trunc, NaN stays NaN
+// (fminf(fmaxf(NaN, -t), t) alone would turn it into -trunc); identical to the plain fmin/fmax on every other value
+__device__ __forceinline__ float clamp_sdf(float v, float trunc) { return v != v ? v : fminf(fmaxf(v, -trunc), trunc); }
+
 __global__ __launch_bounds__(256) void k_targets_fine(const float *__restrict__ sdf, const uint8_t *__restrict__ known,
                                                      int64_t total, float trunc, int masking, float wmg,
                                                      float *__restrict__ tsdf, float *__restrict__ hier_last,
                                                      float *__restrict__ occ, float *__restrict__ w) {
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-    const float t = fminf(fmaxf(sdf[i], -trunc), trunc);          // clamp keeps -inf -> -trunc, like torch.clamp_
+    const float t = clamp_sdf(sdf[i], trunc);
     tsdf[i] = t;
     hier_last[i] = t;
     float o = fabsf(t) < trunc ? 1.f : 0.f;
@@ -304,7 +308,7 @@ __global__ __launch_bounds__(256) void k_targets_coarse(CoarseArgs a) {
       const int64_t o = (((int64_t)b * c0 + z) * c1 + y) * c2 + x;
       a.occ[0][o] = m;
       if (a.w[0]) a.w[0][o] = a.w_f[(((int64_t)b * a.d0 + 2 * z) * a.d1 + 2 * y) * a.d2 + 2 * x];
-      a.hier[0][o] = fminf(fmaxf(a.hier_in[0][o], -a.trunc), a.trunc);
+      a.hier[0][o] = clamp_sdf(a.hier_in[0][o], a.trunc);
     }
     if (a.nlev >= 2) {   // level L-3: max over the 2x2x2 lanes that differ in the low bit of lz, ly, lx
       m = fmaxf(m, __shfl_xor(m, 1));
@@ -316,7 +320,7 @@ __global__ __launch_bounds__(256) void k_targets_coarse(CoarseArgs a) {
         const int64_t o = (((int64_t)b * e0 + zz) * e1 + yy) * e2 + xx;
         a.occ[1][o] = m;
         if (a.w[1]) a.w[1][o] = a.w_f[(((int64_t)b * a.d0 + 4 * zz) * a.d1 + 4 * yy) * a.d2 + 4 * xx];
-        a.hier[1][o] = fminf(fmaxf(a.hier_in[1][o], -a.trunc), a.trunc);
+        a.hier[1][o] = clamp_sdf(a.hier_in[1][o], a.trunc);
       }
       if (a.nlev >= 3) {   // level L-4: the whole brick
         m = fmaxf(m, __shfl_xor(m, 2));
@@ -327,7 +331,7 @@ __global__ __launch_bounds__(256) void k_targets_coarse(CoarseArgs a) {
           const int64_t o = (((int64_t)b * f0 + bz) * f1 + by) * f2 + bx;
           a.occ[2][o] = m;
           if (a.w[2]) a.w[2][o] = a.w_f[(((int64_t)b * a.d0 + 8 * bz) * a.d1 + 8 * by) * a.d2 + 8 * bx];
-          a.hier[2][o] = fminf(fmaxf(a.hier_in[2][o], -a.trunc), a.trunc);
+          a.hier[2][o] = clamp_sdf(a.hier_in[2][o], a.trunc);
         }
       }
     }

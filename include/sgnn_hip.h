@@ -793,6 +793,17 @@ typedef struct sgnn_render_frame {
 int sgnn_render_depth(const float *verts, int nverts, const int32_t *faces, int ntri, const sgnn_render_frame *frames,
                       int nframes, int chunk, int h, int w, float z_clip, float depth_min, float depth_max,
                       int wave_pixels, float *out, int32_t *status, int64_t *counters, sgnn_stream_t stream);
+/* Colour frames with the depth (rules in INTEGRATION.md section N): sgnn_render_depth of a mesh whose vertices carry
+ * a colour, vcolors (nverts, 3) u8 R, G, B.  out is the depth stack of sgnn_render_depth, bit for bit; rgba
+ * (nframes, h, w, 4) u8, memory order R, G, B, A, 4-byte aligned, is the colour stack sgnn_fusecol_integrate takes:
+ * A = 255 where out is finite, (0, 0, 0, 0) elsewhere.  The colour is interpolated perspective-correctly; among
+ * fragments of equal depth the smallest R<<24 | G<<16 | B<<8 wins.  keys: workspace of nframes * h * w u64, 16-byte
+ * aligned, the depth buffer while the call runs (z bits in the high word, the colour in the low word, folded with
+ * one 64-bit unsigned atomic minimum per covered pixel). */
+int sgnn_rendercol_draw(const float *verts, int nverts, const int32_t *faces, int ntri, const sgnn_render_frame *frames,
+                        int nframes, int chunk, int h, int w, float z_clip, float depth_min, float depth_max,
+                        int wave_pixels, float *out, int32_t *status, int64_t *counters, const uint8_t *vcolors,
+                        uint64_t *keys, uint8_t *rgba, sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Mesh-to-mesh distances (sgnn_amd.meshdist; rules in INTEGRATION.md section G): the exact nearest triangle of a
@@ -849,6 +860,15 @@ int sgnn_raycast_bricks(const float *sdf, int dx, int dy, int dz, float band, ui
 int sgnn_raycast_cast(const float *sdf, int dx, int dy, int dz, float band, const uint8_t *bricks,
                       const sgnn_raycast_frame *frames, int nframes, int chunk, int h, int w, float depth_min, float dt,
                       int nsamples, float *depth, float *normal, int64_t *counters, sgnn_stream_t stream);
+/* Colour frames with the depth (rules in INTEGRATION.md section N): sgnn_raycast_cast of a volume that also has a
+ * colour per voxel, colors (dz, dy, dx, 4) u8 R, G, B, A, 4-byte aligned, A != 0 = the voxel has a colour.  depth and
+ * normal are those of sgnn_raycast_cast, bit for bit; rgba (nframes, h, w, 4) u8, 4-byte aligned: at a hit the
+ * weighted mean of the coloured corners of the hit's cell with A = 255, (0, 0, 0, 0) for no hit or no coloured
+ * corner.  Only a ray with a hit reads colours. */
+int sgnn_raycol_cast(const float *sdf, int dx, int dy, int dz, float band, const uint8_t *bricks,
+                     const sgnn_raycast_frame *frames, int nframes, int chunk, int h, int w, float depth_min, float dt,
+                     int nsamples, float *depth, float *normal, int64_t *counters, const uint8_t *colors, uint8_t *rgba,
+                     sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Depth frames tracked against a volume (sgnn_amd.track; rules in INTEGRATION.md section I): the "frame to model"

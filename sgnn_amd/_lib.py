@@ -140,6 +140,8 @@ PROTOTYPES = {
                                 c_vp, c_vp]),
     'sgnn_render_depth': (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_i32,
                                   c_vp, c_vp, c_vp, c_vp]),
+    'sgnn_rendercol_draw': (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32,
+                                    c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'sgnn_meshdist_pack': (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'sgnn_meshdist_count': (c_i32, [c_vp, c_i32, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'sgnn_meshdist_fill': (c_i32, [c_vp, c_i32, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
@@ -149,6 +151,8 @@ PROTOTYPES = {
     'sgnn_raycast_bricks': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp]),
     'sgnn_raycast_cast': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32,
                                   c_i32, c_vp, c_vp, c_vp, c_vp]),
+    'sgnn_raycol_cast': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32,
+                                 c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'sgnn_track_halve': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp]),
     'sgnn_track_normals': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp]),
     'sgnn_track_system': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_f32, c_f32, c_vp, c_vp,

@@ -19,6 +19,10 @@
 // every sample between them does.  A failed check skips sample k alone.  Nothing rests on the accuracy of the
 // estimate: the result is the one of the plain walk, bit for bit.
 //
+// Colour frames of a volume that carries a colour per voxel come from the same kernel text (template parameter
+// COLOR, rules in INTEGRATION.md section N, restated in tests/raycast_color_ref.py): a lane that has a hit fetches
+// the eight R, G, B, A words of the hit's cell once, after the walk.
+//
 // Built with -ffp-contract=off (Makefile): every product and sum is rounded on its own.
 #include <math.h>
 #include "common.h"
@@ -54,6 +58,39 @@ __device__ __forceinline__ bool sample(const Volume &V, float gx, float gy, floa
   const float y0 = x00 + ay * (x01 - x00), y1 = x10 + ay * (x11 - x10);
   v = y0 + az * (y1 - y0);
   return true;
+}
+
+// Section N: the colour at the hit g, from the cell's corners that have one (A != 0); the R, G, B, A bytes of the
+// pixel as one word, 0 = no colour.  colors is the dense (dz, dy, dx) volume of R, G, B, A words.
+__device__ __forceinline__ uint32_t hit_color(const Volume &V, const uint32_t *__restrict__ colors, float gx, float gy,
+                                              float gz) {
+  const float fx = floorf(gx), fy = floorf(gy), fz = floorf(gz);
+  if (!(fx >= 0.f && fx <= (float)(V.dx - 2) && fy >= 0.f && fy <= (float)(V.dy - 2) && fz >= 0.f &&
+        fz <= (float)(V.dz - 2)))
+    return 0u;
+  const int64_t sy = V.dx, sz = (int64_t)V.dx * V.dy;
+  const uint32_t *p = colors + ((int64_t)(int)fz * V.dy + (int)fy) * V.dx + (int)fx;
+  uint32_t c[8];                                    // x fastest, then y, then z
+#pragma unroll
+  for (int i = 0; i < 8; ++i) c[i] = p[(i >> 2) * sz + ((i >> 1) & 1) * sy + (i & 1)];
+  const float ax = gx - fx, ay = gy - fy, az = gz - fz;
+  const float wx[2] = {1.0f - ax, ax}, wy[2] = {1.0f - ay, ay}, wz[2] = {1.0f - az, az};
+  float s = 0.f, n0 = 0.f, n1 = 0.f, n2 = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    // a corner without a colour adds a weight of zero: the sums are those over the counted corners, bit for bit
+    const float w = (c[i] >> 24) ? (wz[i >> 2] * wy[(i >> 1) & 1]) * wx[i & 1] : 0.f;
+    s = s + w;
+    n0 = n0 + w * (float)(c[i] & 255u);
+    n1 = n1 + w * (float)((c[i] >> 8) & 255u);
+    n2 = n2 + w * (float)((c[i] >> 16) & 255u);
+  }
+  if (s == 0.f) return 0u;
+  auto ch = [](float v) {
+    const float r = roundf(v);                      // half away from zero
+    return r >= 255.0f ? 255u : (r >= 0.0f ? (uint32_t)r : 0u);
+  };
+  return ch(__fdiv_rn(n0, s)) | (ch(__fdiv_rn(n1, s)) << 8) | (ch(__fdiv_rn(n2, s)) << 16) | 0xFF000000u;
 }
 
 struct Ray {
@@ -136,12 +173,13 @@ __device__ __forceinline__ long long wave_sum(long long v) {
   return v;                                        // lane 0 holds the sum
 }
 
-template <bool SKIP, bool NORMALS>
+template <bool SKIP, bool NORMALS, bool COLOR>
 __global__ __launch_bounds__(256) void k_raycast(Volume V, const uint8_t *__restrict__ bricks, int nbx, int nby,
                                                 const sgnn_raycast_frame *__restrict__ frames, int f0, int h, int w,
                                                 float depth_min, float dt, int nsamples, float *__restrict__ depth,
                                                 float *__restrict__ normal,
-                                                unsigned long long *__restrict__ counters) {
+                                                unsigned long long *__restrict__ counters,
+                                                const uint32_t *__restrict__ colors, uint32_t *__restrict__ rgba) {
   const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
   const int i = (int)blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
   const int j = (int)blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
@@ -224,6 +262,12 @@ __global__ __launch_bounds__(256) void k_raycast(Volume V, const uint8_t *__rest
       normal[px * 3 + 1] = ny;
       normal[px * 3 + 2] = nz;
     }
+    if (COLOR) {
+      // section N: only a lane with a hit fetches colour, at the point of rule 6
+      uint32_t c = 0u;
+      if (hit > -INFINITY) c = hit_color(V, colors, R.ox + hit * R.dx, R.oy + hit * R.dy, R.oz + hit * R.dz);
+      rgba[px] = c;
+    }
   }
   if (counters) {                                   // kernel argument: the same for every lane
     const long long e = wave_sum(n_eval), s = wave_sum(n_skip);
@@ -247,15 +291,19 @@ SGNN_EXPORT int sgnn_raycast_bricks(const float *sdf, int dx, int dy, int dz, fl
   return SGNN_OK;
 }
 
-SGNN_EXPORT int sgnn_raycast_cast(const float *sdf, int dx, int dy, int dz, float band, const uint8_t *bricks,
-                                  const sgnn_raycast_frame *frames, int nframes, int chunk, int h, int w,
-                                  float depth_min, float dt, int nsamples, float *depth, float *normal,
-                                  int64_t *counters, sgnn_stream_t stream) {
+namespace {
+
+// the launches of both entry points; COLOR: colors (dense R, G, B, A words) is read and rgba written
+template <bool COLOR>
+int cast(const float *sdf, int dx, int dy, int dz, float band, const uint8_t *bricks, const sgnn_raycast_frame *frames,
+         int nframes, int chunk, int h, int w, float depth_min, float dt, int nsamples, float *depth, float *normal,
+         int64_t *counters, const uint8_t *colors, uint8_t *rgba, sgnn_stream_t stream) {
   SGNN_CHECK_ARG(dx >= 1 && dy >= 1 && dz >= 1 && dx <= 65535 && dy <= 65535 && dz <= 65535 && band > 0.f);
   SGNN_CHECK_ARG(nframes >= 0 && h >= 1 && w >= 1 && (int64_t)nframes * h * w < ((int64_t)1 << 31));
   SGNN_CHECK_ARG(dt > 0.f && nsamples >= 1 && nsamples <= (1 << 20));
   if (nframes == 0) return SGNN_OK;
   SGNN_CHECK_ARG(sdf && frames && depth);
+  SGNN_CHECK_ARG(!COLOR || (colors && rgba && (((uintptr_t)colors | (uintptr_t)rgba) & 3) == 0));
   const dim3 tiles((w + 15) / 16, (h + 15) / 16);
   SGNN_CHECK_ARG(tiles.y <= 65535);
   if (chunk <= 0 || chunk > nframes) chunk = nframes;
@@ -263,23 +311,43 @@ SGNN_EXPORT int sgnn_raycast_cast(const float *sdf, int dx, int dy, int dz, floa
   const Volume V{sdf, dx, dy, dz, band};
   const int nbx = (dx + BRICK - 1) / BRICK, nby = (dy + BRICK - 1) / BRICK;
   unsigned long long *ctr = reinterpret_cast<unsigned long long *>(counters);
+  const uint32_t *cw = reinterpret_cast<const uint32_t *>(colors);
+  uint32_t *pw = reinterpret_cast<uint32_t *>(rgba);
   hipStream_t s = (hipStream_t)stream;
   for (int f0 = 0; f0 < nframes; f0 += chunk) {
     const int f1 = f0 + chunk < nframes ? f0 + chunk : nframes;
     const dim3 grid(tiles.x, tiles.y, f1 - f0);
     if (bricks && normal)
-      SGNN_LAUNCH((k_raycast<true, true>), grid, dim3(256), 0, s, V, bricks, nbx, nby, frames, f0, h, w, depth_min, dt,
-                  nsamples, depth, normal, ctr);
+      SGNN_LAUNCH((k_raycast<true, true, COLOR>), grid, dim3(256), 0, s, V, bricks, nbx, nby, frames, f0, h, w,
+                  depth_min, dt, nsamples, depth, normal, ctr, cw, pw);
     else if (bricks)
-      SGNN_LAUNCH((k_raycast<true, false>), grid, dim3(256), 0, s, V, bricks, nbx, nby, frames, f0, h, w, depth_min, dt,
-                  nsamples, depth, normal, ctr);
+      SGNN_LAUNCH((k_raycast<true, false, COLOR>), grid, dim3(256), 0, s, V, bricks, nbx, nby, frames, f0, h, w,
+                  depth_min, dt, nsamples, depth, normal, ctr, cw, pw);
     else if (normal)
-      SGNN_LAUNCH((k_raycast<false, true>), grid, dim3(256), 0, s, V, bricks, nbx, nby, frames, f0, h, w, depth_min, dt,
-                  nsamples, depth, normal, ctr);
+      SGNN_LAUNCH((k_raycast<false, true, COLOR>), grid, dim3(256), 0, s, V, bricks, nbx, nby, frames, f0, h, w,
+                  depth_min, dt, nsamples, depth, normal, ctr, cw, pw);
     else
-      SGNN_LAUNCH((k_raycast<false, false>), grid, dim3(256), 0, s, V, bricks, nbx, nby, frames, f0, h, w, depth_min,
-                  dt, nsamples, depth, normal, ctr);
+      SGNN_LAUNCH((k_raycast<false, false, COLOR>), grid, dim3(256), 0, s, V, bricks, nbx, nby, frames, f0, h, w,
+                  depth_min, dt, nsamples, depth, normal, ctr, cw, pw);
     SGNN_CHECK_LAUNCH();
   }
   return SGNN_OK;
+}
+
+}  // namespace
+
+SGNN_EXPORT int sgnn_raycast_cast(const float *sdf, int dx, int dy, int dz, float band, const uint8_t *bricks,
+                                  const sgnn_raycast_frame *frames, int nframes, int chunk, int h, int w,
+                                  float depth_min, float dt, int nsamples, float *depth, float *normal,
+                                  int64_t *counters, sgnn_stream_t stream) {
+  return cast<false>(sdf, dx, dy, dz, band, bricks, frames, nframes, chunk, h, w, depth_min, dt, nsamples, depth,
+                     normal, counters, nullptr, nullptr, stream);
+}
+
+SGNN_EXPORT int sgnn_raycol_cast(const float *sdf, int dx, int dy, int dz, float band, const uint8_t *bricks,
+                                 const sgnn_raycast_frame *frames, int nframes, int chunk, int h, int w,
+                                 float depth_min, float dt, int nsamples, float *depth, float *normal,
+                                 int64_t *counters, const uint8_t *colors, uint8_t *rgba, sgnn_stream_t stream) {
+  return cast<true>(sdf, dx, dy, dz, band, bricks, frames, nframes, chunk, h, w, depth_min, dt, nsamples, depth,
+                    normal, counters, colors, rgba, stream);
 }

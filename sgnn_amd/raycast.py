@@ -11,6 +11,8 @@ independent NumPy restatement of the tests (tests/raycast_ref.py).
     again = cast_volume(vol, K, poses, (240, 320))                      # (F, h, w) fp32 on the device, -inf = no hit
     depth, normal = cast(sdf, world2grid, vs, K, poses, (240, 320), band, normals=True)
     depth = cast_sparse(locs_zyx, vals, dims_zyx, world2grid, vs, K, poses, (240, 320), band)
+    depth, rgba = cast_volume_color(vol, K, poses, (240, 320))          # a TSDFVolume(color=True): colour frames too
+    depth, rgba = cast_color(sdf, colors, world2grid, vs, K, poses, (240, 320), band)
 
 The host does per-frame geometry only (one 3x4 matrix per frame).
 """
@@ -74,7 +76,30 @@ def cast(sdf, world2grid, voxel_size, intrinsics, cam2world, hw, band, step=0.5,
     cx, cy; cam2world (F, 4, 4); numpy arrays or torch tensors, host or device.  skip: pass over empty space through a
     brick table; chunk: frames per launch (None: DEFAULT_CHUNK); the result depends on neither.  counters: None, or a
     device int64 tensor of 2 that receives samples evaluated and samples skipped (measurements)."""
-    dev = _device(sdf.device if torch.is_tensor(sdf) and sdf.is_cuda else None)
+    return _cast(sdf, None, world2grid, voxel_size, intrinsics, cam2world, hw, band, step, depth_min, depth_max, normals,
+                 skip, chunk, counters)
+
+
+def cast_color(sdf, colors, world2grid, voxel_size, intrinsics, cam2world, hw, band, step=0.5, depth_min=0.4,
+               depth_max=4.0, normals=False, skip=True, chunk=None, counters=None):
+    """cast() of a volume that also has a colour per voxel -> (depth, rgba), or (depth, normal, rgba) with
+    normals=True; rgba (F, h, w, 4) uint8 on the device, the layout TSDFVolume.integrate(color=) takes.
+
+    colors (Z, Y, X, 4) uint8 R, G, B, A, A != 0 = the voxel has a colour, or (Z, Y, X, 3), the layout of
+    TSDFVolume.colors() and of marching cubes: every voxel then counts as coloured.  At a hit the colour is the
+    weighted mean of the coloured corners of the hit's cell with A = 255; a ray without a
+    hit, or a hit whose cell has no coloured corner, gets (0, 0, 0, 0).  depth and normal are cast()'s, bit for bit;
+    every other argument as cast()."""
+    shape = tuple(colors.shape)
+    if len(shape) != 4 or shape[:3] != tuple(sdf.shape) or shape[3] not in (3, 4):
+        raise ValueError('colors must be (Z, Y, X, 3 | 4) for sdf %s, got %s' % (tuple(sdf.shape), shape))
+    return _cast(sdf, colors, world2grid, voxel_size, intrinsics, cam2world, hw, band, step, depth_min, depth_max,
+                 normals, skip, chunk, counters)
+
+
+def _cast(sdf, colors, world2grid, voxel_size, intrinsics, cam2world, hw, band, step, depth_min, depth_max, normals,
+          skip, chunk, counters):
+    dev = _device(next((x.device for x in (sdf, colors) if torch.is_tensor(x) and x.is_cuda), None))
     if len(tuple(sdf.shape)) != 3:
         raise ValueError('sdf must be (Z, Y, X), got %s' % (tuple(sdf.shape),))
     dz, dy, dx = (int(v) for v in sdf.shape)
@@ -108,16 +133,29 @@ def cast(sdf, world2grid, voxel_size, intrinsics, cam2world, hw, band, step=0.5,
     vol = _to_device(sdf, torch.float32, dev)
     depth = torch.empty((nf, h, w), dtype=torch.float32, device=dev)
     normal = torch.empty((nf, h, w, 3), dtype=torch.float32, device=dev) if normals else None
+    rgba = None
+    if colors is not None:
+        col = _to_device(colors, torch.uint8, dev)
+        if col.shape[3] == 3:                                            # every voxel counts as coloured
+            col = torch.cat([col, torch.full_like(col[..., :1], 255)], 3).contiguous()
+        rgba = torch.empty((nf, h, w, 4), dtype=torch.uint8, device=dev)
     if nf:
         bricks = None
         if skip:
             bricks = torch.empty(((dz + 7) // 8, (dy + 7) // 8, (dx + 7) // 8), dtype=torch.uint8, device=dev)
             _lib.call('sgnn_raycast_bricks', vol.data_ptr(), dx, dy, dz, float(band), bricks.data_ptr())
         dev_table = torch.from_numpy(table.view(np.uint8)).to(dev)
-        _lib.call('sgnn_raycast_cast', vol.data_ptr(), dx, dy, dz, float(band), _lib.ptr(bricks), dev_table.data_ptr(),
-                  nf, int(DEFAULT_CHUNK if chunk is None else chunk), h, w, float(dmin), float(dt), ns,
-                  depth.data_ptr(), _lib.ptr(normal), _lib.ptr(counters))
-    return (depth, normal) if normals else depth
+        args = (vol.data_ptr(), dx, dy, dz, float(band), _lib.ptr(bricks), dev_table.data_ptr(), nf,
+                int(DEFAULT_CHUNK if chunk is None else chunk), h, w, float(dmin), float(dt), ns, depth.data_ptr(),
+                _lib.ptr(normal), _lib.ptr(counters))
+        if colors is not None:
+            _lib.call('sgnn_raycol_cast', *args, col.data_ptr(), rgba.data_ptr())
+        else:
+            _lib.call('sgnn_raycast_cast', *args)
+    out = (depth, normal) if normals else (depth,)
+    if colors is not None:
+        return out + (rgba,)
+    return out if normals else depth
 
 
 def cast_volume(vol, intrinsics, cam2world, hw, band=None, **kwargs):
@@ -125,6 +163,18 @@ def cast_volume(vol, intrinsics, cam2world, hw, band=None, **kwargs):
     product) unless given.  depth_min / depth_max default to cast()'s, not to the volume's."""
     band = np.float32(3.0) * vol.voxel_size if band is None else band
     return cast(vol.sdf(), vol.world2grid, vol.voxel_size, intrinsics, cam2world, hw, band, **kwargs)
+
+
+def cast_volume_color(vol, intrinsics, cam2world, hw, band=None, **kwargs):
+    """cast_color() of a fusion.TSDFVolume(color=True): cast_volume's geometry, colours from vol.colors() with
+    A = 255 where vol.color_weight() > 0.  ValueError for a volume without colour."""
+    _lib.require_gpu()
+    if vol.color_state() is None:
+        raise ValueError('the volume has no colour: TSDFVolume(..., color=True)')
+    band = np.float32(3.0) * vol.voxel_size if band is None else band
+    alpha = (vol.color_weight() > 0).to(torch.uint8) * 255
+    rgba = torch.cat([vol.colors(), alpha[..., None]], 3).contiguous()
+    return cast_color(vol.sdf(), rgba, vol.world2grid, vol.voxel_size, intrinsics, cam2world, hw, band, **kwargs)
 
 
 def cast_sparse(locs_zyx, vals, dims_zyx, world2grid, voxel_size, intrinsics, cam2world, hw, band, **kwargs):

@@ -56,6 +56,24 @@ def load_ply(path):
     """Host reader for the PLY files marching_cubes.save_to_ply writes: binary little-endian, float x y z vertices
     (further vertex properties are skipped by their declared sizes), `list uchar int vertex_indices` triangles.
     Returns (verts (V, 3) fp32, faces (T, 3) int32).  ValueError names the first header line it cannot handle."""
+    v, _, faces = _read_ply(path)
+    return np.stack([v['x'], v['y'], v['z']], 1).astype(np.float32).reshape(-1, 3), faces
+
+
+def load_ply_colors(path):
+    """load_ply with the vertex colours: (verts (V, 3) fp32, faces (T, 3) int32, vcolors (V, 3) uint8) from the uchar
+    properties red, green, blue that save_to_ply writes: what render_color takes.  ValueError if the file has none."""
+    v, vprops, faces = _read_ply(path)
+    types = dict(vprops)
+    for want in ('red', 'green', 'blue'):
+        if types.get(want) not in ('uchar', 'uint8'):
+            raise ValueError('%s: no uchar vertex property %r (the file has no colours)' % (path, want))
+    verts = np.stack([v['x'], v['y'], v['z']], 1).astype(np.float32).reshape(-1, 3)
+    return verts, faces, np.stack([v['red'], v['green'], v['blue']], 1).astype(np.uint8).reshape(-1, 3)
+
+
+def _read_ply(path):
+    """(vertex records, [(property, type)], faces (T, 3) int32) of a PLY file as load_ply describes it."""
     with open(path, 'rb') as fh:
         blob = fh.read()
     end = blob.find(b'end_header\n')
@@ -90,7 +108,8 @@ def load_ply(path):
             raise ValueError('%s: vertex property %r must be a float' % (path, want))
     if 'vertex' not in counts or 'face' not in counts or not face_ok:
         raise ValueError('%s: needs a vertex element and a face element with vertex_indices' % path)
-    vdt = np.dtype({'names': names, 'formats': ['V%d' % _PLY_SIZES[t] if n not in ('x', 'y', 'z') else '<f4' for n, t in vprops]})
+    vdt = np.dtype({'names': names, 'formats': ['<f4' if n in ('x', 'y', 'z') else 'u1' if _PLY_SIZES[t] == 1 else
+                                                'V%d' % _PLY_SIZES[t] for n, t in vprops]})
     nv, nf = counts['vertex'], counts['face']
     fdt = np.dtype([('n', 'u1'), ('i', '<i4', (3,))])
     if len(blob) < body + nv * vdt.itemsize + nf * fdt.itemsize:
@@ -100,8 +119,7 @@ def load_ply(path):
     if nf and (f['n'] != 3).any():
         raise ValueError('%s: unsupported face %d: %d vertices (triangles only)' % (
             path, int(np.argmax(f['n'] != 3)), int(f['n'][np.argmax(f['n'] != 3)])))
-    return (np.stack([v['x'], v['y'], v['z']], 1).astype(np.float32).reshape(-1, 3),
-            np.ascontiguousarray(f['i']).astype(np.int32).reshape(-1, 3))
+    return v, vprops, np.ascontiguousarray(f['i']).astype(np.int32).reshape(-1, 3)
 
 
 def frame_table(intrinsics, cam2world):
@@ -134,7 +152,25 @@ def render_depth(verts, faces, intrinsics, cam2world, hw, z_clip=0.1, depth_min=
     TSDFVolume.integrate.  chunk: frames per launch (the result does not depend on it; None: DEFAULT_CHUNK).
     counters: None, or a device int64 tensor of 3 that receives triangles drawn per lane, triangles drawn per wave
     and covered pixels (measurements; slower)."""
-    dev = _device(next((x.device for x in (verts, faces) if torch.is_tensor(x) and x.is_cuda), None))
+    return _render(verts, faces, None, intrinsics, cam2world, hw, z_clip, depth_min, depth_max, chunk, counters)
+
+
+def render_color(verts, faces, vcolors, intrinsics, cam2world, hw, z_clip=0.1, depth_min=0.4, depth_max=4.0,
+                 chunk=None, counters=None):
+    """render_depth of a mesh whose vertices carry a colour -> (depth (F, h, w) fp32, rgba (F, h, w, 4) uint8), both
+    on the device: the pair TSDFVolume(color=True).integrate(depth, K, cam2world, color=rgba) takes.
+
+    vcolors (V, 3) uint8 R, G, B, numpy or torch, host or device; every other argument, and every error, as
+    render_depth.  depth is render_depth's, bit for bit.  The colour is interpolated perspective-correctly between
+    the vertices; A = 255 where depth is finite, (0, 0, 0, 0) elsewhere."""
+    if vcolors is None or len(tuple(vcolors.shape)) != 2 or tuple(vcolors.shape) != (int(verts.shape[0]), 3):
+        raise ValueError('vcolors must be (V, 3) for verts %s, got %s' % (
+            tuple(verts.shape), None if vcolors is None else tuple(vcolors.shape)))
+    return _render(verts, faces, vcolors, intrinsics, cam2world, hw, z_clip, depth_min, depth_max, chunk, counters)
+
+
+def _render(verts, faces, vcolors, intrinsics, cam2world, hw, z_clip, depth_min, depth_max, chunk, counters):
+    dev = _device(next((x.device for x in (verts, faces, vcolors) if torch.is_tensor(x) and x.is_cuda), None))
     h, w = (int(v) for v in hw)
     if h < 1 or w < 1 or h > 16384 or w > 16384:
         raise ValueError('unsupported frame size %s' % ((h, w),))
@@ -160,14 +196,22 @@ def render_depth(verts, faces, intrinsics, cam2world, hw, z_clip=0.1, depth_min=
     v = _to_device(verts, torch.float32, dev)
     f = _to_device(faces, torch.int32, dev)
     out = torch.empty((nf, h, w), dtype=torch.float32, device=dev)
+    color = vcolors is not None
+    rgba = torch.empty((nf, h, w, 4), dtype=torch.uint8, device=dev) if color else None
     if nf == 0:
-        return out
+        return (out, rgba) if color else out
     status = torch.zeros(1, dtype=torch.int32, device=dev) if on_device else None
     dev_table = torch.from_numpy(table.view(np.uint8)).to(dev)
-    _lib.call('sgnn_render_depth', v.data_ptr(), nv, f.data_ptr(), nt, dev_table.data_ptr(), nf,
-              int(DEFAULT_CHUNK if chunk is None else chunk), h, w, float(np.float32(z_clip)),
-              float(np.float32(depth_min)), float(np.float32(depth_max)), int(WAVE_PIXELS), out.data_ptr(),
-              _lib.ptr(status), _lib.ptr(counters))
+    args = (v.data_ptr(), nv, f.data_ptr(), nt, dev_table.data_ptr(), nf,
+            int(DEFAULT_CHUNK if chunk is None else chunk), h, w, float(np.float32(z_clip)),
+            float(np.float32(depth_min)), float(np.float32(depth_max)), int(WAVE_PIXELS), out.data_ptr(),
+            _lib.ptr(status), _lib.ptr(counters))
+    if color:
+        c = _to_device(vcolors, torch.uint8, dev)
+        keys = torch.empty((nf, h, w), dtype=torch.int64, device=dev)       # the depth buffer of the call
+        _lib.call('sgnn_rendercol_draw', *args, c.data_ptr(), keys.data_ptr(), rgba.data_ptr())
+    else:
+        _lib.call('sgnn_render_depth', *args)
     if status is not None and int(status.item()) & STATUS_INDEX_RANGE:
         raise ValueError('face index out of range [0, %d)' % nv)
-    return out
+    return (out, rgba) if color else out

@@ -1016,6 +1016,30 @@ int sgnn_vox_tsdf(const float *dist, const int32_t *face, int64_t n, float voxel
                   sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Euclidean feature transform of a dense seed mask (sgnn_amd.edt; rules in INTEGRATION.md section O): for every voxel
+ * of a (dz, dy, dx) volume, x fastest, the nearest seed and the squared distance to it, exactly, in integers.  Among
+ * seeds at the same squared distance the one with the smallest linear index (sz * dy + sy) * dx + sx wins.  Every
+ * dimension is at most SGNN_EDT_MAX_DIM and there are fewer than 2^31 voxels; a volume without voxels is a no-op.
+ * max_dist2 < 0: no cap; otherwise a voxel whose nearest seed is farther than max_dist2 (squared, in voxels) has none,
+ * and every other voxel gets what it gets without a cap.  The caller chains three passes:
+ *   sgnn_edt_rows -> feat[p] = the nearest seed of p inside p's row, equal distances to the smaller x, packed as
+ *                    sz << 20 | sy << 10 | sx, or -1 (mask: u8, non-zero = seed)
+ *   sgnn_edt_axis -> one pass along y (axis 1) or z (axis 0) over the features of the pass before: the candidate of
+ *                    p = the feature of a voxel of p's column that is nearest to p, equal distances to the smaller
+ *                    packed value.  With dist2 and nearest NULL it writes packed features to feat_out; with both
+ *                    given it is the last pass and writes dist2 (i32) and nearest (i32 linear index), -1 / -1 for
+ *                    none, and feat_out is not used.  No output may be feat_in.
+ * x, then y, then z gives the rule above (the lexicographically smallest (sz, sy, sx) among the nearest).
+ *   sgnn_edt_fill -> out[p] = colors[nearest[p]] (3 bytes) where nearest[p] is in [0, n), else 0; out is not colors
+ * Integer arithmetic only and no atomics: the same input gives the same output.
+ * ------------------------------------------------------------------------- */
+#define SGNN_EDT_MAX_DIM 1024
+int sgnn_edt_rows(const uint8_t *mask, int dz, int dy, int dx, int max_dist2, int32_t *feat, sgnn_stream_t stream);
+int sgnn_edt_axis(const int32_t *feat_in, int dz, int dy, int dx, int axis, int max_dist2, int32_t *feat_out,
+                  int32_t *dist2, int32_t *nearest, sgnn_stream_t stream);
+int sgnn_edt_fill(const uint8_t *colors, const int32_t *nearest, int64_t n, uint8_t *out, sgnn_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Evaluation metrics on the device.
  * ------------------------------------------------------------------------- */
 /* IoU ingredients of one hierarchy level (torch/loss.py:84-120 compute_iou_sparse_dense, fed as in

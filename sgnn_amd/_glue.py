@@ -1,7 +1,7 @@
 """Host glue shared by the device-side tools (fusion, render, meshdist, raycast, track, marching_cubes,
-components, simplify, voxelize): where an input ends up, and the allocate-and-call wrappers of the shared mesh entry
-points (csrc/mesh_tables.hip) and of sgnn_compact_mask.  Plumbing only; every helper does what its callers wrote out
-before.
+components, simplify, voxelize, edt): where an input ends up, and the allocate-and-call wrappers of the shared mesh
+entry points (csrc/mesh_tables.hip) and of sgnn_compact_mask.  Plumbing only; every helper does what its callers wrote
+out before.
 """
 import numpy as np
 import torch

@@ -175,6 +175,9 @@ PROTOTYPES = {
     'sgnn_vox_nearest': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_vp, c_vp,
                                  c_vp, c_i64, c_vp, c_vp, c_vp]),
     'sgnn_vox_tsdf': (c_i32, [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp]),
+    'sgnn_edt_rows': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    'sgnn_edt_axis': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    'sgnn_edt_fill': (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     'sgnn_iou_counts': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'sgnn_l1_tgtsurf_ws_bytes': (c_i64, []),
     'sgnn_l1_tgtsurf': (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp, c_i64, c_vp]),

@@ -17,11 +17,10 @@
 // square root are correctly rounded, so distances match the fp32 restatement bit for bit whatever the grid.
 #include <math.h>
 #include "common.h"
+#include "box_lists.h"  // the cell walk of k_meshdist_cells, shared with voxelize.hip
 #include "tri_dist.h"   // rule 2, shared with voxelize.hip
 
 namespace {
-
-constexpr int WAVE_CELLS = 256;   // a face whose box touches more cells is listed by its whole wave
 
 // rule 5: the cell of a coordinate, clamped into the grid (NaN -> 0)
 __device__ __forceinline__ int cell_of(float x, float lo, float cell, int n) {
@@ -79,44 +78,19 @@ __global__ __launch_bounds__(256) void k_meshdist_cells(const float *__restrict_
                                                        const int32_t *__restrict__ offsets,
                                                        int32_t *__restrict__ counts, int32_t *__restrict__ refs) {
   const int t = (int)(blockIdx.x * 256 + threadIdx.x);
-  int x0 = 0, y0 = 0, z0 = 0, sx = 0, sy = 0, sz = 0;              // first cell and cells per axis; sx == 0: nothing
+  CellRange r = {0, 0, 0, 0, 0, 0};
   if (t < ntri) {
     const float *bx = boxes + (int64_t)t * 6;
     if (bx[0] <= bx[3]) {                                         // false for an ignored face
-      x0 = cell_of(bx[0], lox, cell, nx);
-      y0 = cell_of(bx[1], loy, cell, ny);
-      z0 = cell_of(bx[2], loz, cell, nz);
-      sx = cell_of(bx[3], lox, cell, nx) - x0 + 1;
-      sy = cell_of(bx[4], loy, cell, ny) - y0 + 1;
-      sz = cell_of(bx[5], loz, cell, nz) - z0 + 1;
+      r.x0 = cell_of(bx[0], lox, cell, nx);
+      r.y0 = cell_of(bx[1], loy, cell, ny);
+      r.z0 = cell_of(bx[2], loz, cell, nz);
+      r.sx = cell_of(bx[3], lox, cell, nx) - r.x0 + 1;
+      r.sy = cell_of(bx[4], loy, cell, ny) - r.y0 + 1;
+      r.sz = cell_of(bx[5], loz, cell, nz) - r.z0 + 1;
     }
   }
-  auto put = [&](int c, int f) {
-    const int k = atomicAdd(counts + c, 1);
-    if (FILL) refs[offsets[c] + k] = f;
-  };
-  const int64_t total = (int64_t)sx * sy * sz;
-  const bool big = total > WAVE_CELLS;
-  if (sx > 0 && !big)
-    for (int z = z0; z < z0 + sz; ++z)
-      for (int y = y0; y < y0 + sy; ++y)
-        for (int x = x0; x < x0 + sx; ++x) put((z * ny + y) * nx + x, t);
-  // a face whose box touches many cells is spread over its wave, 64 consecutive cells per step
-  unsigned long long todo = __ballot(big);
-  const int lane = (int)(threadIdx.x & 63);
-  while (todo) {
-    const int src = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(todo));
-    todo &= todo - 1;
-    const int bx0 = __builtin_amdgcn_readlane(x0, src), by0 = __builtin_amdgcn_readlane(y0, src);
-    const int bz0 = __builtin_amdgcn_readlane(z0, src), bsx = __builtin_amdgcn_readlane(sx, src);
-    const int bsy = __builtin_amdgcn_readlane(sy, src), bsz = __builtin_amdgcn_readlane(sz, src);
-    const int f = __builtin_amdgcn_readlane(t, src);
-    const int64_t n = (int64_t)bsx * bsy * bsz;
-    for (int64_t q = lane; q < n; q += 64) {
-      const int x = (int)(q % bsx), y = (int)((q / bsx) % bsy), z = (int)(q / ((int64_t)bsx * bsy));
-      put(((bz0 + z) * ny + (by0 + y)) * nx + (bx0 + x), f);
-    }
-  }
+  list_in_cells<FILL>(r, t, nx, ny, offsets, counts, refs);      // every lane: it holds a ballot
 }
 
 template <bool COUNT>

@@ -19,6 +19,7 @@
 // Built with -ffp-contract=off (Makefile): distances and faces equal meshdist's bit for bit (tri_dist.h is shared).
 #include <math.h>
 #include "common.h"
+#include "box_lists.h"  // the brick walk of k_vox_bricks, shared with meshdist.hip
 #include "first_table.h"
 #include "tri_dist.h"
 
@@ -26,7 +27,6 @@ namespace {
 
 constexpr int BRICK = 8;                  // voxels per brick axis; 512 voxels, two per lane of a 256-thread workgroup
 constexpr int BATCH = SGNN_VOX_BATCH;     // face records staged per round: 128 * (48 + 24 + 4) B = 9.5 KiB of LDS
-constexpr int WAVE_BRICKS = 256;          // a face whose box touches more bricks is listed by its whole wave
 constexpr double Q32 = 4294967296.0;      // 2^32: the fixed point of the pseudo-normal sums
 
 // The voxel box of a face: its vertex box grown by band and a margin of 2^-16 of the largest magnitude involved, far
@@ -80,45 +80,20 @@ __global__ __launch_bounds__(256) void k_vox_bricks(const float *__restrict__ bo
                                                    int32_t *__restrict__ counts, int32_t *__restrict__ refs) {
   const int t = (int)(blockIdx.x * 256 + threadIdx.x);
   const int nbx = (dx + BRICK - 1) / BRICK, nby = (dy + BRICK - 1) / BRICK;
-  int x0 = 0, y0 = 0, z0 = 0, sx = 0, sy = 0, sz = 0;              // first brick and bricks per axis; sx == 0: nothing
+  CellRange r = {0, 0, 0, 0, 0, 0};                               // in bricks
   if (t < ntri) {
     float lo[3], hi[3];
     vox_box(boxes + (int64_t)t * 6, band, (float)max(dx, max(dy, dz)), lo, hi);
     int x1, y1, z1;
-    if (vox_range(lo[0], hi[0], dx, x0, x1) && vox_range(lo[1], hi[1], dy, y0, y1) &&
-        vox_range(lo[2], hi[2], dz, z0, z1)) {
-      x0 /= BRICK, y0 /= BRICK, z0 /= BRICK;
-      sx = x1 / BRICK - x0 + 1;
-      sy = y1 / BRICK - y0 + 1;
-      sz = z1 / BRICK - z0 + 1;
+    if (vox_range(lo[0], hi[0], dx, r.x0, x1) && vox_range(lo[1], hi[1], dy, r.y0, y1) &&
+        vox_range(lo[2], hi[2], dz, r.z0, z1)) {
+      r.x0 /= BRICK, r.y0 /= BRICK, r.z0 /= BRICK;
+      r.sx = x1 / BRICK - r.x0 + 1;
+      r.sy = y1 / BRICK - r.y0 + 1;
+      r.sz = z1 / BRICK - r.z0 + 1;
     }
   }
-  auto put = [&](int c, int f) {
-    const int k = atomicAdd(counts + c, 1);
-    if (FILL) refs[offsets[c] + k] = f;
-  };
-  const int64_t total = (int64_t)sx * sy * sz;
-  const bool big = total > WAVE_BRICKS;
-  if (sx > 0 && !big)
-    for (int z = z0; z < z0 + sz; ++z)
-      for (int y = y0; y < y0 + sy; ++y)
-        for (int x = x0; x < x0 + sx; ++x) put((z * nby + y) * nbx + x, t);
-  // a face whose box touches many bricks is spread over its wave, 64 consecutive bricks per step
-  unsigned long long todo = __ballot(big);
-  const int lane = (int)(threadIdx.x & 63);
-  while (todo) {
-    const int src = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(todo));
-    todo &= todo - 1;
-    const int bx0 = __builtin_amdgcn_readlane(x0, src), by0 = __builtin_amdgcn_readlane(y0, src);
-    const int bz0 = __builtin_amdgcn_readlane(z0, src), bsx = __builtin_amdgcn_readlane(sx, src);
-    const int bsy = __builtin_amdgcn_readlane(sy, src), bsz = __builtin_amdgcn_readlane(sz, src);
-    const int f = __builtin_amdgcn_readlane(t, src);
-    const int64_t n = (int64_t)bsx * bsy * bsz;
-    for (int64_t q = lane; q < n; q += 64) {
-      const int x = (int)(q % bsx), y = (int)((q / bsx) % bsy), z = (int)(q / ((int64_t)bsx * bsy));
-      put(((bz0 + z) * nby + (by0 + y)) * nbx + (bx0 + x), f);
-    }
-  }
+  list_in_cells<FILL>(r, t, nbx, nby, offsets, counts, refs);    // every lane: it holds a ballot
 }
 
 // the undirected edge (i, j) as a key; never all ones, since both are vertex indices below 2^31

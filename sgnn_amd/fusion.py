@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib, data
-from ._glue import compact, device as _device, host as _host, to_device as _to_device
+from ._glue import cameras, compact, device as _device, host as _host, to_device as _to_device
 
 # struct sgnn_fuse_frame (include/sgnn_hip.h)
 FRAME_DTYPE = np.dtype([('m', '<f4', (12,)), ('intr', '<f4', (4,)), ('box', '<i4', (6,)), ('offset', '<i8')])
@@ -205,11 +205,8 @@ class TSDFVolume(object):
 
     def frame_table(self, intrinsics, cam2world, hw):
         """Host table of sgnn_fuse_frame records for F frames of size hw = (h, w)."""
-        k = _host(intrinsics, np.float32).reshape(-1, 4)
-        c2w = _host(cam2world, np.float64).reshape(-1, 4, 4)
+        k, c2w = cameras(intrinsics, cam2world)
         nf = k.shape[0]
-        if c2w.shape[0] != nf:
-            raise ValueError('%d intrinsics for %d poses' % (nf, c2w.shape[0]))
         t = np.zeros(nf, dtype=FRAME_DTYPE)
         with np.errstate(all='ignore'):
             ok = np.isfinite(c2w).all(axis=(1, 2))

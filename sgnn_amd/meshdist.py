@@ -18,9 +18,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._glue import device as _device, host as _host, to_device as _to_device
+from ._glue import binned_lists, mesh_shape, mesh_upload, pack_faces, to_device as _to_device
 
-STATUS_INDEX_RANGE = 1      # SGNN_STATUS_COORD_RANGE
 MAX_CELLS_AXIS = 1024       # cells per axis and in all that an index accepts (rule 5)
 MAX_CELLS = 1 << 26
 F32 = np.float32
@@ -28,22 +27,12 @@ F32 = np.float32
 
 def _mesh(verts, faces):
     """Checked device tensors (verts fp32 (V, 3), faces int32 (T, 3)) and whether the faces came from the device."""
-    dev = _device(next((x.device for x in (verts, faces) if torch.is_tensor(x) and x.is_cuda), None))
-    for name, x, cols in (('verts', verts, 3), ('faces', faces, 3)):
-        shape = tuple(x.shape)
-        if len(shape) != 2 or shape[1] != cols:
-            raise ValueError('%s must be (N, %d), got %s' % (name, cols, shape))
-    nv, nt = int(verts.shape[0]), int(faces.shape[0])
+    dev, (nv, nt) = mesh_shape(verts, faces)
     if nt == 0:
         raise ValueError('the mesh has no faces')
     if nt * 3 >= 2 ** 31:
         raise ValueError('3 T = %d does not fit 31 bits' % (nt * 3))
-    on_device = torch.is_tensor(faces) and faces.is_cuda
-    if not on_device:
-        fh = _host(faces, np.int64)
-        if fh.min() < 0 or fh.max() >= nv:
-            raise ValueError('face index out of range [0, %d)' % nv)
-    return _to_device(verts, torch.float32, dev), _to_device(faces, torch.int32, dev), on_device, dev
+    return mesh_upload(verts, faces, nv, dev) + (dev,)
 
 
 class _Packed:
@@ -51,16 +40,9 @@ class _Packed:
 
     def __init__(self, verts, faces):
         v, f, on_device, dev = _mesh(verts, faces)
-        nv, nt = int(v.shape[0]), int(f.shape[0])
+        nt = int(f.shape[0])
         self.device, self.ntri = dev, nt
-        self.records = torch.empty((nt, 12), dtype=torch.float32, device=dev)
-        self.boxes = torch.empty((nt, 6), dtype=torch.float32, device=dev)
-        self.usable = torch.empty(nt, dtype=torch.uint8, device=dev)
-        status = torch.zeros(1, dtype=torch.int32, device=dev) if on_device else None
-        _lib.call('sgnn_meshdist_pack', v.data_ptr(), nv, f.data_ptr(), nt, self.records.data_ptr(),
-                  self.boxes.data_ptr(), self.usable.data_ptr(), _lib.ptr(status))
-        if status is not None and int(status.item()) & STATUS_INDEX_RANGE:
-            raise ValueError('face index out of range [0, %d)' % nv)
+        self.records, self.boxes, self.usable = pack_faces(v, f, on_device, dev)
         ids = torch.nonzero(self.usable).reshape(-1)
         self.n_usable = int(ids.numel())
         if self.n_usable == 0:
@@ -112,19 +94,9 @@ class TriangleIndex:
         self.dims = tuple(int(s) for s in span)                              # nx, ny, nz
         ncell = self.dims[0] * self.dims[1] * self.dims[2]
         grid = (float(self.lo[0]), float(self.lo[1]), float(self.lo[2]), float(self.cell)) + self.dims
-        counts = torch.zeros(ncell, dtype=torch.int32, device=self.device)
-        _lib.call('sgnn_meshdist_count', p.boxes.data_ptr(), p.ntri, *grid, counts.data_ptr())
-        offsets = torch.zeros(ncell + 1, dtype=torch.int64, device=self.device)
-        torch.cumsum(counts, 0, out=offsets[1:])
-        self.n_refs = int(offsets[-1].item())
-        if self.n_refs >= 2 ** 31:
-            raise ValueError('%d (face, cell) references do not fit 31 bits at cell = %g: choose a larger cell'
-                             % (self.n_refs, self.cell))
-        self.offsets = offsets.to(torch.int32)
-        self.refs = torch.empty(max(self.n_refs, 1), dtype=torch.int32, device=self.device)
-        counts.zero_()
-        _lib.call('sgnn_meshdist_fill', p.boxes.data_ptr(), p.ntri, *grid, self.offsets.data_ptr(), counts.data_ptr(),
-                  self.refs.data_ptr())
+        self.offsets, self.refs, self.n_refs = binned_lists(
+            'sgnn_meshdist_count', 'sgnn_meshdist_fill', (p.boxes.data_ptr(), p.ntri) + grid, ncell, self.device,
+            '%%d (face, cell) references do not fit 31 bits at cell = %g: choose a larger cell' % self.cell)
 
     def _keys(self, pts):
         """Approximate linear cell of every point: the order of the sorted hand-over only."""

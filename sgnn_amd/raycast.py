@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._glue import device as _device, host as _host, to_device as _to_device
+from ._glue import camera_shapes, cameras, device as _device, host as _host, to_device as _to_device
 
 # struct sgnn_raycast_frame (include/sgnn_hip.h)
 FRAME_DTYPE = np.dtype([('g', '<f4', (12,)), ('intr', '<f4', (4,))])
@@ -34,11 +34,8 @@ def frame_table(intrinsics, cam2world, world2grid):
     """Host table of sgnn_raycast_frame records (rule 1): rows 0..2 of world2grid . cam2world, formed in fp64 and
     rounded to fp32, and fx, fy, cx, cy.  A pose that is not finite (or whose product is not finite in fp32) gets NaN
     rows: its frame stays empty."""
-    k = _host(intrinsics, np.float32).reshape(-1, 4)
-    c2w = _host(cam2world, np.float64).reshape(-1, 4, 4)
+    k, c2w = cameras(intrinsics, cam2world)
     w2g = _host(world2grid, np.float64).reshape(4, 4)
-    if c2w.shape[0] != k.shape[0]:
-        raise ValueError('%d intrinsics for %d poses' % (k.shape[0], c2w.shape[0]))
     t = np.zeros(k.shape[0], dtype=FRAME_DTYPE)
     with np.errstate(all='ignore'):
         g = (w2g @ c2w)[:, :3, :].astype(np.float32)
@@ -116,10 +113,7 @@ def _cast(sdf, colors, world2grid, voxel_size, intrinsics, cam2world, hw, band, 
             raise ValueError('%s must be positive' % name)
     if not (np.isfinite(dmin) and np.isfinite(dmax)) or dmax < dmin:
         raise ValueError('depth_min = %s, depth_max = %s is not a range' % (depth_min, depth_max))
-    if np.ndim(intrinsics) != 2 or tuple(np.shape(intrinsics))[1:] != (4,):
-        raise ValueError('intrinsics must be (F, 4), got %s' % (tuple(np.shape(intrinsics)),))
-    if np.ndim(cam2world) != 3 or tuple(np.shape(cam2world))[1:] != (4, 4):
-        raise ValueError('cam2world must be (F, 4, 4), got %s' % (tuple(np.shape(cam2world)),))
+    camera_shapes(intrinsics, cam2world)
     table = frame_table(intrinsics, cam2world, world2grid)
     nf = int(table.shape[0])
     if nf * h * w >= 2 ** 31:

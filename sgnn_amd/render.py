@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._glue import device as _device, host as _host, to_device as _to_device
+from ._glue import camera_shapes, cameras, mesh_shape, mesh_upload, to_device as _to_device
 
 # struct sgnn_render_frame (include/sgnn_hip.h)
 FRAME_DTYPE = np.dtype([('m', '<f4', (12,)), ('intr', '<f4', (4,))])
@@ -125,10 +125,7 @@ def _read_ply(path):
 def frame_table(intrinsics, cam2world):
     """Host table of sgnn_render_frame records: rows 0..2 of inv(cam2world), formed in fp64 and rounded to fp32, and
     fx, fy, cx, cy.  A non-finite pose gets NaN rows (its frame stays empty)."""
-    k = _host(intrinsics, np.float32).reshape(-1, 4)
-    c2w = _host(cam2world, np.float64).reshape(-1, 4, 4)
-    if c2w.shape[0] != k.shape[0]:
-        raise ValueError('%d intrinsics for %d poses' % (k.shape[0], c2w.shape[0]))
+    k, c2w = cameras(intrinsics, cam2world)
     t = np.zeros(k.shape[0], dtype=FRAME_DTYPE)
     ok = np.isfinite(c2w).all(axis=(1, 2))
     m = np.full((k.shape[0], 3, 4), np.nan, dtype=np.float32)
@@ -170,31 +167,18 @@ def render_color(verts, faces, vcolors, intrinsics, cam2world, hw, z_clip=0.1, d
 
 
 def _render(verts, faces, vcolors, intrinsics, cam2world, hw, z_clip, depth_min, depth_max, chunk, counters):
-    dev = _device(next((x.device for x in (verts, faces, vcolors) if torch.is_tensor(x) and x.is_cuda), None))
     h, w = (int(v) for v in hw)
     if h < 1 or w < 1 or h > 16384 or w > 16384:
         raise ValueError('unsupported frame size %s' % ((h, w),))
-    for name, x, cols in (('verts', verts, 3), ('faces', faces, 3)):
-        shape = tuple(x.shape)
-        if len(shape) != 2 or shape[1] != cols:
-            raise ValueError('%s must be (N, %d), got %s' % (name, cols, shape))
-    if np.ndim(intrinsics) != 2 or tuple(np.shape(intrinsics))[1:] != (4,):
-        raise ValueError('intrinsics must be (F, 4), got %s' % (tuple(np.shape(intrinsics)),))
-    if np.ndim(cam2world) != 3 or tuple(np.shape(cam2world))[1:] != (4, 4):
-        raise ValueError('cam2world must be (F, 4, 4), got %s' % (tuple(np.shape(cam2world)),))
+    dev, (nv, nt) = mesh_shape(verts, faces, vcolors)
+    camera_shapes(intrinsics, cam2world)
     if not float(z_clip) > 0.0:
         raise ValueError('z_clip must be positive')
     table = frame_table(intrinsics, cam2world)
-    nf, nv, nt = int(table.shape[0]), int(verts.shape[0]), int(faces.shape[0])
+    nf = int(table.shape[0])
     if nt * 3 >= 2 ** 31 or nf * h * w >= 2 ** 31:
         raise ValueError('3 T = %d or F h w = %d does not fit 31 bits' % (nt * 3, nf * h * w))
-    on_device = torch.is_tensor(faces) and faces.is_cuda
-    if not on_device and nt:
-        fh = _host(faces, np.int64)
-        if fh.min() < 0 or fh.max() >= nv:
-            raise ValueError('face index out of range [0, %d)' % nv)
-    v = _to_device(verts, torch.float32, dev)
-    f = _to_device(faces, torch.int32, dev)
+    v, f, on_device = mesh_upload(verts, faces, nv, dev)
     out = torch.empty((nf, h, w), dtype=torch.float32, device=dev)
     color = vcolors is not None
     rgba = torch.empty((nf, h, w, 4), dtype=torch.uint8, device=dev) if color else None

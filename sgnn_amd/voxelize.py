@@ -20,11 +20,11 @@ import numpy as np
 import torch
 
 from . import _lib, fusion
-from ._glue import compact, device as _device, host as _host, to_device as _to_device
+from ._glue import binned_lists, compact, host as _host, mesh_shape, mesh_upload, pack_faces
 
 BRICK = 8               # voxels per brick axis (csrc/voxelize.hip)
 FACE_BATCH = 128        # SGNN_VOX_BATCH of include/sgnn_hip.h: face records a brick stages through LDS at a time
-WAVE_BRICKS = 256       # a face whose voxel box touches more bricks is listed by its whole wave (csrc/voxelize.hip)
+WAVE_BRICKS = 256       # a face whose voxel box touches more bricks is listed by its whole wave (csrc/box_lists.h)
 MAX_BAND = 65535.0
 F32 = np.float32
 
@@ -32,26 +32,25 @@ Result = namedtuple('Result', ['dist', 'face'])
 
 
 def _check(verts, faces, dims_xyz, band):
-    dev = _device(next((x.device for x in (verts, faces) if torch.is_tensor(x) and x.is_cuda), None))
-    for name, x in (('verts', verts), ('faces', faces)):
-        shape = tuple(x.shape)
-        if len(shape) != 2 or shape[1] != 3:
-            raise ValueError('%s must be (N, 3), got %s' % (name, shape))
+    dev, (nv, nt) = mesh_shape(verts, faces)
     dims = tuple(int(d) for d in dims_xyz)
     if len(dims) != 3 or min(dims) < 1 or max(dims) > 65535 or dims[0] * dims[1] * dims[2] >= 2 ** 31:
         raise ValueError('unsupported volume dimensions %s' % (dims,))
     band = float(F32(band))
     if not 0.0 <= band <= MAX_BAND:
         raise ValueError('band must be in [0, %g] voxels, got %r' % (MAX_BAND, band))
-    nv, nt = int(verts.shape[0]), int(faces.shape[0])
     if nt * 3 >= 2 ** 31 or nv >= 2 ** 31:
         raise ValueError('the mesh does not fit 31-bit indices')
-    on_device = torch.is_tensor(faces) and faces.is_cuda
-    if nt and not on_device:
-        fh = _host(faces, np.int64)
-        if fh.min() < 0 or fh.max() >= nv:
-            raise ValueError('face index out of range [0, %d)' % nv)
-    return _to_device(verts, torch.float32, dev), _to_device(faces, torch.int32, dev), on_device, dims, band, dev
+    return mesh_upload(verts, faces, nv, dev) + (dims, band, dev)
+
+
+def _brick_lists(boxes, nt, band, dims, dev):
+    """The faces of every 8x8x8 brick (CSR): (offsets (bricks + 1,) int32, refs int32, n_refs)."""
+    dx, dy, dz = dims
+    nbricks = -(-dx // BRICK) * -(-dy // BRICK) * -(-dz // BRICK)
+    return binned_lists('sgnn_vox_bricks_count', 'sgnn_vox_bricks_fill', (boxes.data_ptr(), nt, band, dx, dy, dz),
+                        nbricks, dev,
+                        '%d (face, brick) references do not fit 31 bits: voxelise a coarser volume or a smaller band')
 
 
 def _signed_distance(v, f, on_device, dims, band, flip, dev):
@@ -61,32 +60,11 @@ def _signed_distance(v, f, on_device, dims, band, flip, dev):
     face = torch.full((dz, dy, dx), -1, dtype=torch.int32, device=dev)
     if nt == 0:
         return Result(dist, face)
-    records = torch.empty((nt, 12), dtype=torch.float32, device=dev)
-    boxes = torch.empty((nt, 6), dtype=torch.float32, device=dev)
-    usable = torch.empty(nt, dtype=torch.uint8, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev) if on_device else None
-    _lib.call('sgnn_meshdist_pack', v.data_ptr(), nv, f.data_ptr(), nt, records.data_ptr(), boxes.data_ptr(),
-              usable.data_ptr(), _lib.ptr(status))
-    if status is not None and int(status.item()) & 1:              # SGNN_STATUS_COORD_RANGE
-        raise ValueError('face index out of range [0, %d)' % nv)
-    # brick lists: count, exclusive scan, fill
-    nbricks = -(-dx // BRICK) * -(-dy // BRICK) * -(-dz // BRICK)
-    counts = torch.zeros(nbricks, dtype=torch.int32, device=dev)
-    _lib.call('sgnn_vox_bricks_count', boxes.data_ptr(), nt, band, dx, dy, dz, counts.data_ptr())
-    sel, nsel = compact((counts > 0).to(torch.uint8), nbricks, dev)
-    if nsel == 0:
+    records, boxes, usable = pack_faces(v, f, on_device, dev)
+    offsets, refs, n_refs = _brick_lists(boxes, nt, band, dims, dev)
+    if n_refs == 0:                                                 # no brick holds a face
         return Result(dist, face)
-    offsets = torch.zeros(nbricks + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(counts, 0, out=offsets[1:])
-    n_refs = int(offsets[-1].item())
-    if n_refs >= 2 ** 31:
-        raise ValueError('%d (face, brick) references do not fit 31 bits: voxelise a coarser volume or a smaller band'
-                         % n_refs)
-    offsets = offsets.to(torch.int32)
-    refs = torch.empty(n_refs, dtype=torch.int32, device=dev)
-    counts.zero_()
-    _lib.call('sgnn_vox_bricks_fill', boxes.data_ptr(), nt, band, dx, dy, dz, offsets.data_ptr(), counts.data_ptr(),
-              refs.data_ptr())
+    sel, nsel = compact((offsets[1:] != offsets[:-1]).to(torch.uint8), offsets.numel() - 1, dev)
     # pseudo-normal tables
     cap = _lib.query('sgnn_weld_slots', 3 * nt)
     vsum = torch.empty((max(nv, 1), 3), dtype=torch.int64, device=dev)

@@ -114,6 +114,43 @@ def test_large_triangles_and_ties(n, cell):
          (exp[0], M.distance_ref(pts, verts, twice[::-1])[1]))
 
 
+WAVE_CELLS = 256            # csrc/box_lists.h: a face whose box touches more cells is listed by its whole wave
+
+
+def lists_equal(verts, faces, cell):
+    """The index's CSR lists against meshdist_ref.GridRef: offsets entry by entry, every cell's faces as sorted sets
+    (the order inside a cell is the atomics').  Returns the number of cells each face is listed in."""
+    index = meshdist.TriangleIndex(verts, faces, cell)
+    grid = M.GridRef(verts, faces, index.cell)
+    assert index.dims == grid.dims and index.n_refs == grid.offsets[-1] == len(grid.refs)
+    assert index.offsets.dtype == torch.int32 and index.refs.dtype == torch.int32
+    offsets, refs = index.offsets.cpu().numpy(), index.refs.cpu().numpy()[:index.n_refs]
+    assert np.array_equal(offsets, grid.offsets)
+    cells = np.repeat(np.arange(len(offsets) - 1), np.diff(offsets))
+    assert np.array_equal(refs[np.lexsort((refs, cells))], grid.refs)
+    return np.bincount(grid.refs, minlength=len(faces))
+
+
+def test_the_cell_lists_of_faces_listed_by_their_wave():
+    """The room at cell = 0.1: its twelve wall triangles span a thousand cells each (the smallest wall is 3.2 x 2.6 m),
+    the faces of its furniture tens to hundreds; one face with a NaN vertex sits among them and is in no list."""
+    verts, faces = RR.tessellate_room(1)
+    verts = np.concatenate([verts, [[np.nan, 0.5, 0.5]]]).astype(F32)
+    faces = np.concatenate([faces[:5], [[len(verts) - 1, 0, 1]], faces[5:]]).astype(np.int32)
+    per_face = lists_equal(verts, faces, 0.1)
+    assert per_face[5] == 0 and (np.delete(per_face, 5) >= 1).all()
+    assert (per_face[:13] > 3 * WAVE_CELLS).sum() == 12 and per_face.sum() > 100 * len(faces)
+
+
+def test_the_cell_lists_of_big_and_small_faces_in_one_wave():
+    verts, faces = RR.triangle_soup(300)
+    per_face = lists_equal(verts, faces, None)
+    big = per_face > WAVE_CELLS
+    assert per_face.min() >= 1 and 10 <= big.sum() <= len(faces) // 2
+    waves = np.arange(len(faces)) // 64
+    assert any(big[waves == w].any() and not big[waves == w].all() for w in np.unique(waves))
+
+
 def test_ignored_faces_and_bad_points():
     verts, faces, pts, exp = soup_case()
     verts, faces, pts = verts.copy(), faces[:1200].copy(), pts[:2000].copy()

@@ -99,16 +99,22 @@ def test_a_face_that_touches_more_bricks_than_one_thread_lists(dims):
     assert len(touched) > 60
 
 
-def test_big_and_small_faces_in_one_wave():
-    """Two faces over the threshold, small faces before, between and after them, all listed by the same wave; the
-    second big face is listed only in part of the volume."""
-    dims = (72, 72, 56)
+def wave_mix():
+    """Eight faces for a (72, 72, 56) volume: 2 and 6 are big, the others small."""
     needle, nf = VR.needle_tetrahedron(offset=(40.37, 8.61, 20.29))
     quad = np.array([[50.3, 52.7, 4.1], [61.6, 53.9, 6.3], [60.2, 64.8, 8.9], [49.4, 63.1, 6.2]], F32)
     big = np.array([[-3.2, -2.1, 1.3], [80.7, 9.2, 29.9], [18.4, 77.3, 54.8],
                     [21.3, 70.9, 3.2], [69.8, 66.1, 50.7], [66.2, 18.4, 47.5]], F32)
     verts = np.concatenate([needle, quad, big])
     faces = np.concatenate([nf[:2], [[8, 9, 10]], nf[2:], [[4, 5, 6]], [[11, 12, 13]], [[4, 6, 7]]]).astype(np.int32)
+    return verts, faces
+
+
+def test_big_and_small_faces_in_one_wave():
+    """Two faces over the threshold, small faces before, between and after them, all listed by the same wave; the
+    second big face is listed only in part of the volume."""
+    dims = (72, 72, 56)
+    verts, faces = wave_mix()
     assert len(faces) < 64
     for t in (2, 6):
         assert bricks_touched(verts, faces[t], dims, 3.0) > voxelize.WAVE_BRICKS
@@ -116,6 +122,50 @@ def test_big_and_small_faces_in_one_wave():
     assert all(bricks_touched(verts, faces[t], dims, 3.0) <= 64 for t in (0, 1, 3, 4, 5, 7))
     dist, face, _ = check(verts, faces, dims, 3.0)
     assert set(np.unique(face)) == {-1} | set(range(8))
+
+
+def sorted_lists(offsets, refs):
+    """The refs of a CSR list in ascending order inside every cell: the order inside a cell is the atomics'."""
+    cell = np.repeat(np.arange(len(offsets) - 1), np.diff(offsets))
+    return refs[np.lexsort((refs, cell))]
+
+
+@pytest.mark.parametrize('band', [0.0, 3.0])
+@pytest.mark.parametrize('dims', [(20, 9, 33), (69, 75, 53)])
+def test_the_brick_lists_themselves(dims, band):
+    """voxelize._brick_lists against voxelize_ref.brick_lists_ref: offsets equal, every brick's faces equal as sets.
+    One wave holds faces that span the volume (listed by the wave in the larger volume, where they touch more than
+    WAVE_BRICKS bricks, by their lane in the smaller), small faces, one face wholly outside, one overhanging the
+    x = 0 side and one with a NaN vertex.  Neither volume is a multiple of the brick."""
+    verts, faces = wave_mix()
+    verts = verts * (np.array(dims, F32) / np.array([72, 72, 56], F32))              # made for a (72, 72, 56) volume
+    nv = len(verts)
+    more = np.array([[100.5, 3, 3], [104, 9.1, 3], [101, 4, 8.3],                     # wholly outside
+                     [-9.2, 4.1, 10.3], [2.6, 6.2, 12.9], [-4.1, 7.7, 17.2],          # overhangs x = 0
+                     [np.nan, 3, 3]], F32)
+    faces = np.concatenate([faces, [[nv, nv + 1, nv + 2], [nv + 3, nv + 4, nv + 5], [nv + 6, 0, 1]]]).astype(np.int32)
+    verts = np.concatenate([verts, more])
+    outside, overhang, ignored = 8, 9, 10
+    tri = verts[faces]
+    boxes = np.concatenate([tri.min(1), tri.max(1)], 1)
+    boxes[ignored] = [np.inf] * 3 + [-np.inf] * 3
+    packed = meshdist._Packed(verts, faces)
+    assert np.array_equal(bits(packed.boxes.cpu().numpy()), bits(boxes))
+    want_offsets, want_refs = VR.brick_lists_ref(boxes, dims, band)
+    per_face = np.bincount(want_refs, minlength=len(faces))
+    assert per_face[outside] == per_face[ignored] == 0 and per_face[overhang] > 0
+    assert (per_face[:8] > 0).all() if band else (per_face[[2, 5, 6, 7]] > 0).all()      # a thin face may hold no voxel
+    assert per_face.max() == -(-dims[0] // 8) * -(-dims[1] // 8) * -(-dims[2] // 8)         # the whole volume
+    if dims == (69, 75, 53):
+        assert (per_face[[2, 6]] > voxelize.WAVE_BRICKS).all() and (per_face[[0, 1, 3, 4, 5, 7]] <= 64).all()
+    else:
+        assert per_face.max() <= voxelize.WAVE_BRICKS
+    for _ in range(2):
+        offsets, refs, n_refs = voxelize._brick_lists(packed.boxes, len(faces), float(F32(band)), dims, packed.device)
+        assert offsets.dtype == torch.int32 and refs.dtype == torch.int32 and n_refs == want_offsets[-1]
+        offsets, refs = offsets.cpu().numpy(), refs.cpu().numpy()[:n_refs]
+        assert np.array_equal(offsets, want_offsets)
+        assert np.array_equal(sorted_lists(offsets, refs), want_refs)
 
 
 @pytest.mark.parametrize('nfaces,band', [(voxelize.FACE_BATCH + 1, 3.0), (3 * voxelize.FACE_BATCH, 1.5)])

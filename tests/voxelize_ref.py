@@ -193,6 +193,37 @@ def signed_distance_ref(verts_grid, faces, dims_xyz, band, flip=False):
 
 
 # ---------------------------------------------------------------------------------------------------------
+# "Bricks and the hot kernel": the brick lists
+# ---------------------------------------------------------------------------------------------------------
+def brick_lists_ref(boxes, dims_xyz, band, brick=8):
+    """CSR lists of the faces of every brick, bricks in raster order (x fastest): (offsets (bricks + 1,) int64, refs
+    int64, ascending inside a brick).  boxes (T, 6) fp32 vertex boxes lo, hi, (+inf, -inf) for an ignored face.  A
+    face's voxel box is its vertex box grown by band + 2^-16 m in fp32, m the largest of band, the largest dimension
+    and the box's magnitudes; the face is listed in every brick that holds a voxel lo <= i <= hi of that box."""
+    bx = np.asarray(boxes, F32).reshape(-1, 6)
+    dims = np.array(dims_xyz, np.int64)
+    nb = -(-dims // brick)
+    band = F32(band)
+    bricks, ids = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]
+    for t in range(len(bx)):
+        if not bx[t, 0] <= bx[t, 3]:
+            continue
+        m = max(band, F32(dims.max()), np.abs(bx[t]).max())
+        marg = band + m * F32(2.0 ** -16)
+        first = np.maximum(np.ceil(bx[t, :3] - marg), F32(0))
+        last = np.minimum(np.floor(bx[t, 3:] + marg), (dims - 1).astype(F32))
+        if not (first <= last).all():
+            continue
+        r = [np.arange(int(first[k]) // brick, int(last[k]) // brick + 1) for k in range(3)]
+        b = ((r[2][:, None, None] * nb[1] + r[1][None, :, None]) * nb[0] + r[0][None, None, :]).ravel()
+        bricks.append(b)
+        ids.append(np.full(len(b), t, np.int64))
+    bricks, ids = np.concatenate(bricks), np.concatenate(ids)
+    order = np.lexsort((ids, bricks))
+    return np.concatenate([[0], np.cumsum(np.bincount(bricks, minlength=int(nb.prod())))]), ids[order]
+
+
+# ---------------------------------------------------------------------------------------------------------
 # fp64 checks of the restatement itself
 # ---------------------------------------------------------------------------------------------------------
 def distance64(points, verts, faces):

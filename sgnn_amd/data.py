@@ -279,7 +279,9 @@ class DeviceBatchLoader(object):
 
     chunk mode  (target_path == ''): `batch_size` .sdfs files per batch, as SceneDataset + collate.
     scene mode  (target_path given): one (.sdf input, .sdf target, .knw) triple per batch with the reference's
-                padding (scene_dataloader.py:80-98); batch_size must be 1 (scenes differ in size).
+                padding (scene_dataloader.py:80-98); batch_size must be 1 (scenes differ in size).  Each file's
+                block is divided by that file's voxel size, world2grid is the target file's, and the .knw must
+                have the target's dimensions (ValueError otherwise).
     """
 
     def __init__(self, files, batch_size, truncation, num_hierarchy_levels=4, max_input_height=0, target_path='',
@@ -331,6 +333,10 @@ class DeviceBatchLoader(object):
             blocks = {'input': [(l[0], 0) for l in lays], 'target': [(l[1], 0) for l in lays]}
             known_src = [l[2] for l in lays]
             ref = lays[0][1]
+            for l in lays:                  # the known volume is packed and viewed with the target's dimensions
+                if (l[2].dimx, l[2].dimy, l[2].dimz) != (l[1].dimx, l[1].dimy, l[1].dimz):
+                    raise ValueError('the .knw dimensions %d x %d x %d differ from its target scene\'s %d x %d x %d' % (
+                        l[2].dimx, l[2].dimy, l[2].dimz, l[1].dimx, l[1].dimy, l[1].dimz))
         plan, off = {'blocks': {}, 'nb': nb, 'names': names}, 0
         copies = []                                                  # (dst offset, source uint8 view)
         for key, lst in blocks.items():
@@ -352,12 +358,21 @@ class DeviceBatchLoader(object):
         for s, l in enumerate(known_src):
             copies.append((off + s * vol, l.known_bytes()))
         off = _align(off + nb * vol)
+        # every block is divided by the voxel size of the file it came from, and world2grid is the target file's
+        # (scene_dataloader.py:70-73: the second load_scene overwrites it); a chunk is one file, so both coincide
+        tgt = 0 if self.is_chunks else 1
         vs = np.array([l[0].voxelsize for l in lays], dtype=np.float32)
-        w2g = np.stack([l[0].world2grid for l in lays]).astype(np.float32)
+        w2g = np.stack([l[tgt].world2grid for l in lays]).astype(np.float32)
         plan['voxelsize'], plan['world2grid'] = off, _align(off + 4 * nb)
         copies.append((plan['voxelsize'], vs.view(np.uint8)))
         copies.append((plan['world2grid'], w2g.reshape(-1).view(np.uint8)))
         off = _align(plan['world2grid'] + 64 * nb)
+        plan['voxelsize_tgt'] = plan['voxelsize']
+        if not self.is_chunks:
+            vs_tgt = np.array([l[tgt].voxelsize for l in lays], dtype=np.float32)
+            plan['voxelsize_tgt'] = off
+            copies.append((off, vs_tgt.view(np.uint8)))
+            off = _align(off + 4 * nb)
         plan['dims'] = (ref.dimz, ref.dimy, ref.dimx)
         plan['in_dims'] = (lays[0][0].dimz, lays[0][0].dimy, lays[0][0].dimx)
         staging = self._staging_buffer(off)
@@ -392,6 +407,7 @@ class DeviceBatchLoader(object):
             return raw[off:off + nbytes].view(dtype)
 
         vs = sect(plan['voxelsize'], 4 * nb, torch.float32)
+        vs_tgt = sect(plan['voxelsize_tgt'], 4 * nb, torch.float32)
         w2g = sect(plan['world2grid'], 64 * nb, torch.float32).view(nb, 4, 4).clone()
         dz, dy, dx = plan['dims']
         chunk = self.is_chunks
@@ -425,7 +441,7 @@ class DeviceBatchLoader(object):
         def dense_of(key, dims):
             n_, ol, ov, os_ = plan['blocks'][key]
             vol = torch.full((nb, 1) + tuple(dims), -float('inf'), dtype=torch.float32, device=dev)
-            _lib.call('sgnn_io_scatter_dense', raw[ol:].data_ptr(), raw[ov:].data_ptr(), vs.data_ptr(),
+            _lib.call('sgnn_io_scatter_dense', raw[ol:].data_ptr(), raw[ov:].data_ptr(), vs_tgt.data_ptr(),
                       raw[os_:].data_ptr(), nb, n_, dims[0], dims[1], dims[2], tgt_limit, vol.data_ptr())
             return vol
 

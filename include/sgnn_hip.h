@@ -1040,6 +1040,39 @@ int sgnn_edt_axis(const int32_t *feat_in, int dz, int dy, int dx, int axis, int 
 int sgnn_edt_fill(const uint8_t *colors, const int32_t *nearest, int64_t n, uint8_t *out, sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Point clouds with known sensor origins fused into a scan volume (sgnn_amd.points; rules in INTEGRATION.md
+ * section P).  The volume is the (sdf, weight, free_ctr[, color]) state of the fusion block above.  points (nrays, 3)
+ * and origins (norigins, 3) f32 world metres; origin_id (nrays) i32 or NULL (all 0); world2grid / grid2world: host
+ * float[12], rows 0..2 of the fp32 matrices; obb: host float[12] as in sgnn_fuse_integrate, or NULL.  One call of
+ * points.integrate chains:
+ *   sgnn_points_count -> counts[r] = the number of half-voxel samples of ray r (0: the ray is ignored, or its segment
+ *                        cannot touch the grid); box (device int32[8]) = x0, x1, y0, y1, z0, z1, inclusive, of the
+ *                        voxels the call's segments can touch (x0 > x1: none), box[6] = 1 if an origin id is outside
+ *                        [0, norigins) (such rays are ignored), box[7] = 0
+ *   (offsets = exclusive scan of counts, nrays + 1 int64, made by the caller)
+ *   sgnn_points_walk  -> one lane per sample; integer atomic adds into accumulators that cover the box only (host
+ *                        int32[6], read back from sgnn_points_count), x fastest: acc_s int64 = sum q wi,
+ *                        acc_wf u64 = free count << 32 | sum wi, acc_c 4 u64 per voxel = sum R wi, G wi, B wi, wi
+ *                        (NULL iff colors (nrays, channels = 3 | 4) u8 is NULL).  The accumulators are zero before
+ *                        the first walk of a call; several walks over parts of the rays add up.  max_samples: the
+ *                        caller's upper bound on offsets[nrays], which only sizes the launch.
+ *   sgnn_points_fold  -> the accumulators folded into the volume as ONE observation per voxel
+ * Integer atomics only: the same rays in any order, in any split, give the same bits.
+ * ------------------------------------------------------------------------- */
+#define SGNN_POINTS_MAX_RAYS (1ll << 28)
+int sgnn_points_count(const float *points, const float *origins, const int32_t *origin_id, int64_t nrays, int norigins,
+                      const float *world2grid, int dx, int dy, int dz, float voxel_size, float depth_min,
+                      float depth_max, int carve, int32_t *counts, int32_t *box, sgnn_stream_t stream);
+int sgnn_points_walk(const float *points, const float *origins, const int32_t *origin_id, const uint8_t *colors,
+                     int channels, int64_t nrays, int norigins, const int64_t *offsets, int64_t max_samples,
+                     const float *world2grid, const float *grid2world, const float *obb, int dx, int dy, int dz,
+                     float voxel_size, float depth_min, float depth_max, int carve, const int32_t *box, int64_t *acc_s,
+                     uint64_t *acc_wf, uint64_t *acc_c, sgnn_stream_t stream);
+int sgnn_points_fold(float *sdf, uint8_t *weight, int32_t *free_ctr, uint16_t *color, int dx, int dy, int dz,
+                     float voxel_size, const int32_t *box, const int64_t *acc_s, const uint64_t *acc_wf,
+                     const uint64_t *acc_c, sgnn_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Evaluation metrics on the device.
  * ------------------------------------------------------------------------- */
 /* IoU ingredients of one hierarchy level (torch/loss.py:84-120 compute_iou_sparse_dense, fed as in

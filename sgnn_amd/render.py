@@ -72,8 +72,9 @@ def load_ply_colors(path):
     return verts, faces, np.stack([v['red'], v['green'], v['blue']], 1).astype(np.uint8).reshape(-1, 3)
 
 
-def _read_ply(path):
-    """(vertex records, [(property, type)], faces (T, 3) int32) of a PLY file as load_ply describes it."""
+def _read_ply(path, need_faces=True):
+    """(vertex records, [(property, type)], faces (T, 3) int32) of a PLY file as load_ply describes it.  need_faces
+    False (points.load_ply_points): the face element may be missing, and faces is then (0, 3)."""
     with open(path, 'rb') as fh:
         blob = fh.read()
     end = blob.find(b'end_header\n')
@@ -106,7 +107,9 @@ def _read_ply(path):
     for want in ('x', 'y', 'z'):
         if want not in names or dict(vprops)[want] not in ('float', 'float32'):
             raise ValueError('%s: vertex property %r must be a float' % (path, want))
-    if 'vertex' not in counts or 'face' not in counts or not face_ok:
+    if not need_faces and 'vertex' in counts and 'face' not in counts:
+        counts['face'] = 0
+    elif 'vertex' not in counts or 'face' not in counts or not face_ok:
         raise ValueError('%s: needs a vertex element and a face element with vertex_indices' % path)
     vdt = np.dtype({'names': names, 'formats': ['<f4' if n in ('x', 'y', 'z') else 'u1' if _PLY_SIZES[t] == 1 else
                                                 'V%d' % _PLY_SIZES[t] for n, t in vprops]})

@@ -1073,6 +1073,27 @@ int sgnn_points_fold(float *sdf, uint8_t *weight, int32_t *free_ctr, uint16_t *c
                      const uint64_t *acc_c, sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * A TSDF volume's state moved to another grid (sgnn_amd.regrid; rules in INTEGRATION.md section Q).  Both volumes are
+ * the (sdf, weight, free_ctr[, color]) state of the fusion block above, (dz, dy, dx) with x fastest.  map: host
+ * float[12], rows 0..2 of A = src.world2grid . inv(dst.world2grid), which takes a destination voxel to source voxel
+ * coordinates.  linear: 1 = rule Q.5, 0 = rule Q.4 (nearest).  skip: 1 = a block whose destination box provably misses
+ * the source grid takes the short path; the result never depends on it.  shape: the destination brick of a wave,
+ * 0 = 4 x 4 x 4, 1 = 8 x 8 x 1, 2 = 64 x 1 x 1; the result never depends on it.
+ *   sgnn_regrid_resample -> every destination voxel is written; color pointers both NULL or both set
+ *   sgnn_regrid_merge    -> the resampled state is folded into the destination (rule Q.8); colour is folded only
+ *                           where both pointers are set
+ * The two volumes must not share memory.
+ * ------------------------------------------------------------------------- */
+int sgnn_regrid_resample(const float *src_sdf, const uint8_t *src_weight, const int32_t *src_free,
+                         const uint16_t *src_color, int sdx, int sdy, int sdz, const float *map, int linear, int skip,
+                         int shape, float *dst_sdf, uint8_t *dst_weight, int32_t *dst_free, uint16_t *dst_color,
+                         int ddx, int ddy, int ddz, sgnn_stream_t stream);
+int sgnn_regrid_merge(const float *src_sdf, const uint8_t *src_weight, const int32_t *src_free,
+                      const uint16_t *src_color, int sdx, int sdy, int sdz, const float *map, int linear, int skip,
+                      int shape, float *dst_sdf, uint8_t *dst_weight, int32_t *dst_free, uint16_t *dst_color, int ddx,
+                      int ddy, int ddz, sgnn_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Evaluation metrics on the device.
  * ------------------------------------------------------------------------- */
 /* IoU ingredients of one hierarchy level (torch/loss.py:84-120 compute_iou_sparse_dense, fed as in

@@ -15,39 +15,23 @@
 //   k_fuse_emit_block     kept voxels -> (x,y,z) u32 + metric sdf f32, the .sdf block layout
 //   k_fuse_emit_rows      kept voxels -> [z,y,x,0] int64 rows + sdf/vs features (the collated scene input)
 //   k_fuse_known          u8 known codes of the .knw file
-// Compaction between flag and emit is sgnn_compact_mask (stable: raster order, x fastest).
+// Compaction between flag and emit is sgnn_compact_mask (stable: raster order, x fastest).  What this file shares with
+// points.hip and regrid.hip is written once in tsdf.h: the OBB test, the affine row, the observation rule (truncation,
+// clamp, weight ramp) and the layout of the colour record.  The per-frame float fold of k_fuse_integrate is its own.
 //
 // Built with -ffp-contract=off (Makefile): every product and sum below is rounded on its own, so the fp32
 // restatement in the tests reproduces sdf, weight, free counter and colour record bit for bit.
 #include <math.h>
 #include "common.h"
+#include "tsdf.h"
 
 namespace {
 
 // workgroup brick of the integration: 64 x 4 x 1 voxels, x contiguous (state loads / stores coalesce)
 constexpr int BRICK_X = 64, BRICK_Y = 4;
 
-struct FuseObb {
-  int on;
-  float a[3];      // corner
-  float e[3][3];   // edge vectors
-  float ee[3];     // dot(e_k, e_k), formed on the host in the same order as below
-};
-
 __device__ __forceinline__ bool box_hits_brick(const int32_t *b, int x0, int x1, int y0, int y1, int k) {
   return b[0] <= x1 && b[1] >= x0 && b[2] <= y1 && b[3] >= y0 && b[4] <= k && b[5] >= k;
-}
-
-// 0 <= dot(q - a, e_k) <= dot(e_k, e_k) for k = 0, 1, 2; dot in the order (x*x' + y*y') + z*z'
-__device__ __forceinline__ bool obb_contains(const FuseObb &o, float qx, float qy, float qz) {
-  const float rx = qx - o.a[0], ry = qy - o.a[1], rz = qz - o.a[2];
-  bool in = true;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float d = (rx * o.e[k][0] + ry * o.e[k][1]) + rz * o.e[k][2];
-    in = in && d >= 0.f && d <= o.ee[k];
-  }
-  return in;
 }
 
 __global__ __launch_bounds__(256) void k_fuse_depth_raw(const uint16_t *__restrict__ raw, int64_t npix, int hr, int wr,
@@ -126,17 +110,17 @@ __global__ __launch_bounds__(256) void k_fuse_bilateral(const float *__restrict_
 // is read with scalar loads, the brick test needs no lane), so a frame whose box misses the brick costs a few
 // scalar instructions and a brick that no frame of the chunk touches neither loads nor stores its state.
 //
-// COLOR: `color` holds one uint2 per voxel, four 16-bit fields R, G, B (8.8 fixed point) and the colour weight; `rgba`
-// is the colour stack, 4 bytes per pixel on the depth stack's pixel grid, so a pixel has the same byte offset in
-// both.  A sample that was not clamped on the free-space side and whose pixel has A != 0 folds its colour with the
-// weight of the geometry update.  The colour fetch sits behind all the tests: only lanes that will use it ask for it.
+// COLOR: `color` holds one record per voxel (tsdf.h); `rgba` is the colour stack, 4 bytes per pixel on the depth stack's
+// pixel grid, so a pixel has the same byte offset in both.  A sample that was not clamped on the free-space side and
+// whose pixel has A != 0 folds its colour with the weight of the geometry update.  The colour fetch sits behind all the
+// tests: only lanes that will use it ask for it.
 template <bool COLOR>
 __global__ __launch_bounds__(256) void k_fuse_integrate(float *__restrict__ sdf, uint8_t *__restrict__ weight,
                                                        int32_t *__restrict__ freec, uint2 *__restrict__ color,
                                                        int dx, int dy, const float *__restrict__ depth,
                                                        const uint8_t *__restrict__ rgba, int h, int w,
                                                        const sgnn_fuse_frame *__restrict__ fr, int f0, int f1,
-                                                       float vs, float dmin, float dmax, FuseObb obb) {
+                                                       float vs, float dmin, float dmax, TsdfObb obb) {
   const int x0 = blockIdx.x * BRICK_X, y0 = blockIdx.y * BRICK_Y, k = blockIdx.z;
   const int x1 = min(x0 + BRICK_X - 1, dx - 1), y1 = min(y0 + BRICK_Y - 1, dy - 1);
   bool any = false;
@@ -156,26 +140,22 @@ __global__ __launch_bounds__(256) void k_fuse_integrate(float *__restrict__ sdf,
     wt = weight[v];
     fc = freec[v];
     if constexpr (COLOR) {
-      const uint2 c = color[v];
-      q[0] = (float)(c.x & 0xFFFFu);
-      q[1] = (float)(c.x >> 16);
-      q[2] = (float)(c.y & 0xFFFFu);
-      wc = (int)(c.y >> 16);
+      const TsdfColor c = tsdf_color_unpack(color[v]);
+#pragma unroll
+      for (int t = 0; t < 3; ++t) q[t] = (float)c.q[t];
+      wc = (int)c.w;
     }
   }
   const float fi = (float)i, fj = (float)j, fk = (float)k;
-  const bool eligible = inside && (!obb.on || obb_contains(obb, fi, fj, fk));
+  const bool eligible = inside && (!obb.on || tsdf_obb_contains(obb, fi, fj, fk));
   const uint32_t frame_bytes = (uint32_t)h * (uint32_t)w * 4u;
-  const float trunc0 = vs * 3.0f;
 
   for (int f = f0; f < f1; ++f) {
     const sgnn_fuse_frame &F = fr[f];
     if (!box_hits_brick(F.box, x0, x1, y0, y1, k)) continue;
     const bool inbox = eligible && i >= F.box[0] && i <= F.box[1] && j >= F.box[2] && j <= F.box[3];
-    const float *m = F.m;
-    const float px3 = ((m[0] * fi + m[1] * fj) + m[2] * fk) + m[3];
-    const float py3 = ((m[4] * fi + m[5] * fj) + m[6] * fk) + m[7];
-    const float pz = ((m[8] * fi + m[9] * fj) + m[10] * fk) + m[11];
+    const float px3 = tsdf_affine_row(F.m, 0, fi, fj, fk), py3 = tsdf_affine_row(F.m, 1, fi, fj, fk);
+    const float pz = tsdf_affine_row(F.m, 2, fi, fj, fk);
     const float px = __fdiv_rn(px3 * F.intr[0], pz) + F.intr[2];
     const float py = __fdiv_rn(py3 * F.intr[1], pz) + F.intr[3];
     const float rx = roundf(px), ry = roundf(py);                        // NaN / inf fail both range tests
@@ -188,11 +168,9 @@ __global__ __launch_bounds__(256) void k_fuse_integrate(float *__restrict__ sdf,
     if (!(on_image && d >= dmin && d <= dmax)) continue;
     if (pz < d) ++fc;                                                     // voxel in front of the observation
     const float sd0 = d - pz;
-    const float trunc = trunc0 + d * vs;
+    const float trunc = tsdf_trunc(vs, d);
     if (!(sd0 > -trunc)) continue;
-    const float sd = sd0 >= 0.f ? fminf(trunc, sd0) : fmaxf(-trunc, sd0);
-    const float z01 = __fdiv_rn(d - 0.4f, 4.0f - 0.4f);                 // the weight ramp is fixed to 0.4 .. 4.0 m
-    const float wu = fmaxf(4.5f * (1.0f - z01), 1.0f);
+    const float sd = tsdf_clamp_sd(sd0, trunc), wu = tsdf_ramp(d);
     if (s == -INFINITY) s = sd;
     else s = __fdiv_rn(s * (float)wt + sd * wu, (float)wt + wu);
     wt = min(wt + (int)wu, 255);
@@ -216,7 +194,7 @@ __global__ __launch_bounds__(256) void k_fuse_integrate(float *__restrict__ sdf,
     weight[v] = (uint8_t)wt;
     freec[v] = fc;
     if constexpr (COLOR) {
-      color[v] = make_uint2((uint32_t)q[0] | (uint32_t)q[1] << 16, (uint32_t)q[2] | (uint32_t)wc << 16);
+      color[v] = tsdf_color_pack((uint32_t)q[0], (uint32_t)q[1], (uint32_t)q[2], (uint32_t)wc);
     }
   }
 }
@@ -233,12 +211,10 @@ __global__ __launch_bounds__(256) void k_fusecol_export(const uint2 *__restrict_
     uint8_t wq[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      const uint2 c = t < m ? color[v0 + t] : make_uint2(0u, 0u);
-      const uint32_t wc = c.y >> 16;
-      wq[t] = (uint8_t)wc;
-      o[3 * t] = wc ? (uint8_t)(((c.x & 0xFFFFu) + 128u) >> 8) : 0;
-      o[3 * t + 1] = wc ? (uint8_t)(((c.x >> 16) + 128u) >> 8) : 0;
-      o[3 * t + 2] = wc ? (uint8_t)(((c.y & 0xFFFFu) + 128u) >> 8) : 0;
+      const TsdfColor c = tsdf_color_unpack(t < m ? color[v0 + t] : make_uint2(0u, 0u));
+      wq[t] = (uint8_t)c.w;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) o[3 * t + ch] = c.w ? (uint8_t)tsdf_color8(c.q[ch]) : 0;
     }
     if (m == 4) {                                                         // rgb + 12 g and wcout + 4 g are 4-byte aligned
 #pragma unroll
@@ -357,29 +333,17 @@ static int fuse_integrate(float *sdf, uint8_t *weight, int32_t *free_ctr, uint16
   SGNN_CHECK_ARG(dx >= 1 && dy >= 1 && dz >= 1 && dz <= 65535 && h >= 1 && w >= 1 && nframes >= 0);
   SGNN_CHECK_ARG((int64_t)h * w <= ((int64_t)1 << 29));    // one frame's byte range fits a buffer resource
   if (nframes == 0) return SGNN_OK;
-  SGNN_CHECK_ARG(sdf && weight && free_ctr && depth && frames && voxel_size > 0.f);
-  SGNN_CHECK_ARG((color != nullptr) == (rgba != nullptr) && ((uintptr_t)color & 7) == 0 && ((uintptr_t)rgba & 3) == 0);
-  FuseObb o{};
-  if (obb) {
-    o.on = 1;
-    for (int c = 0; c < 3; ++c) o.a[c] = obb[c];
-    for (int k = 0; k < 3; ++k) {
-      for (int c = 0; c < 3; ++c) o.e[k][c] = obb[3 + 3 * k + c];
-      o.ee[k] = (o.e[k][0] * o.e[k][0] + o.e[k][1] * o.e[k][1]) + o.e[k][2] * o.e[k][2];
-    }
-  }
+  TsdfVol vol;
+  SGNN_CHECK_ARG(tsdf_vol_arg(sdf, weight, free_ctr, color, vol) && depth && frames && voxel_size > 0.f);
+  SGNN_CHECK_ARG((color != nullptr) == (rgba != nullptr) && ((uintptr_t)rgba & 3) == 0);
+  const TsdfObb o = tsdf_obb_arg(obb);
   if (chunk <= 0 || chunk > nframes) chunk = nframes;
   const dim3 grid((dx + BRICK_X - 1) / BRICK_X, (dy + BRICK_Y - 1) / BRICK_Y, dz);
+  const auto kernel = color ? k_fuse_integrate<true> : k_fuse_integrate<false>;
   for (int f0 = 0; f0 < nframes; f0 += chunk) {
     const int f1 = f0 + chunk < nframes ? f0 + chunk : nframes;
-    if (color) {
-      SGNN_LAUNCH(k_fuse_integrate<true>, grid, dim3(256), 0, (hipStream_t)stream, sdf, weight, free_ctr,
-                  reinterpret_cast<uint2 *>(color), dx, dy, depth, rgba, h, w, frames, f0, f1, voxel_size, depth_min,
-                  depth_max, o);
-    } else {
-      SGNN_LAUNCH(k_fuse_integrate<false>, grid, dim3(256), 0, (hipStream_t)stream, sdf, weight, free_ctr,
-                  (uint2 *)nullptr, dx, dy, depth, rgba, h, w, frames, f0, f1, voxel_size, depth_min, depth_max, o);
-    }
+    SGNN_LAUNCH(kernel, grid, dim3(256), 0, (hipStream_t)stream, vol.sdf, vol.weight, vol.freec, vol.color, dx, dy, depth,
+                rgba, h, w, frames, f0, f1, voxel_size, depth_min, depth_max, o);
     SGNN_CHECK_LAUNCH();
   }
   return SGNN_OK;

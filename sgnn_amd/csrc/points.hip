@@ -15,25 +15,16 @@
 //                    sample n-1 for the duplicate test, and adds to integer accumulators with global atomics: one 64-bit
 //                    add for the fixed-point sdf sum, one 64-bit add for (free count << 32 | weight), four more for a
 //                    colour.  Integer sums do not depend on the arrival order: the result has no run-to-run noise.
-//   k_points_fold    one lane per voxel of the box: accumulators -> the volume's running mean, once per call
+//   k_points_fold    one lane per voxel of the box: accumulators -> the volume's running mean, once per call: the fold
+//                    of tsdf.h, as regrid.hip's merge (tsdf.h also has fusion.hip's OBB test, affine map and rule D.5)
 // The accumulators cover the box only: 16 bytes per box voxel, 48 with colour.
 //
 // Built with -ffp-contract=off (Makefile): every product and sum below is rounded on its own.
 #include <math.h>
 #include "common.h"
+#include "tsdf.h"
 
 namespace {
-
-struct PtsAffine {
-  float m[12];     // rows 0..2 of a 4x4, row-major
-};
-
-struct PtsObb {
-  int on;
-  float a[3];
-  float e[3][3];
-  float ee[3];     // dot(e_k, e_k), formed on the host in the same order as below
-};
 
 struct PtsBox {
   int lo[3], n[3];   // first voxel and extent per axis (x, y, z)
@@ -52,23 +43,6 @@ struct PtsRay {
 };
 
 constexpr float PTS_MAX_SAMPLES = 16777216.0f;      // (float)n is exact below 2^24
-
-// ((m0 x + m1 y) + m2 z) + m3 per row: the order of fusion._affine
-__device__ __forceinline__ void pts_affine(const PtsAffine &a, float x, float y, float z, float (&out)[3]) {
-#pragma unroll
-  for (int r = 0; r < 3; ++r) out[r] = ((a.m[4 * r] * x + a.m[4 * r + 1] * y) + a.m[4 * r + 2] * z) + a.m[4 * r + 3];
-}
-
-__device__ __forceinline__ bool pts_obb_contains(const PtsObb &o, float qx, float qy, float qz) {
-  const float rx = qx - o.a[0], ry = qy - o.a[1], rz = qz - o.a[2];
-  bool in = true;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float d = (rx * o.e[k][0] + ry * o.e[k][1]) + rz * o.e[k][2];
-    in = in && d >= 0.f && d <= o.ee[k];
-  }
-  return in;
-}
 
 // rules P.1 - P.5 up to the sample count; false = the ray is ignored
 __device__ __forceinline__ bool pts_ray(const float *__restrict__ points, const float *__restrict__ origins,
@@ -93,9 +67,8 @@ __device__ __forceinline__ bool pts_ray(const float *__restrict__ points, const 
   R.dir[0] = __fdiv_rn(vx, d);
   R.dir[1] = __fdiv_rn(vy, d);
   R.dir[2] = __fdiv_rn(vz, d);
-  R.trunc = g.vs * 3.0f + d * g.vs;
-  const float z01 = __fdiv_rn(d - 0.4f, 4.0f - 0.4f);                   // the weight ramp of rule D.5
-  R.wi = (int)fmaxf(4.5f * (1.0f - z01), 1.0f);
+  R.trunc = tsdf_trunc(g.vs, d);
+  R.wi = (int)tsdf_ramp(d);
   R.t0 = g.carve ? g.dmin : fmaxf(d - R.trunc, 0.f);
   R.te = d + R.trunc;
   const float nf = floorf(__fdiv_rn(R.te - R.t0, g.vs * 0.5f));
@@ -105,11 +78,11 @@ __device__ __forceinline__ bool pts_ray(const float *__restrict__ points, const 
 }
 
 // the voxel of sample n as three integer-valued floats (NaN / inf possible: they fail the grid test)
-__device__ __forceinline__ void pts_sample_voxel(const PtsRay &R, const PtsAffine &w2g, float half, int n,
+__device__ __forceinline__ void pts_sample_voxel(const PtsRay &R, const TsdfAffine &w2g, float half, int n,
                                                  float (&v)[3]) {
   const float t = R.t0 + (float)n * half;
   float gq[3];
-  pts_affine(w2g, R.o[0] + R.dir[0] * t, R.o[1] + R.dir[1] * t, R.o[2] + R.dir[2] * t, gq);
+  tsdf_affine(w2g.m, R.o[0] + R.dir[0] * t, R.o[1] + R.dir[1] * t, R.o[2] + R.dir[2] * t, gq);
 #pragma unroll
   for (int c = 0; c < 3; ++c) v[c] = roundf(gq[c]);
 }
@@ -123,7 +96,7 @@ __global__ void k_points_box_init(int32_t *box) {
 __global__ __launch_bounds__(256) void k_points_count(const float *__restrict__ points,
                                                      const float *__restrict__ origins,
                                                      const int32_t *__restrict__ origin_id, int64_t nrays,
-                                                     int norigins, PtsAffine w2g, PtsGrid g,
+                                                     int norigins, TsdfAffine w2g, PtsGrid g,
                                                      int32_t *__restrict__ counts, int32_t *__restrict__ box) {
   const int64_t stride = (int64_t)gridDim.x * 256;
   const int dims[3] = {g.dx, g.dy, g.dz};
@@ -134,8 +107,8 @@ __global__ __launch_bounds__(256) void k_points_count(const float *__restrict__ 
     int n = 0;
     if (pts_ray(points, origins, origin_id, r, norigins, g, R, bad_id)) {
       float a[3], b[3];
-      pts_affine(w2g, R.o[0] + R.dir[0] * R.t0, R.o[1] + R.dir[1] * R.t0, R.o[2] + R.dir[2] * R.t0, a);
-      pts_affine(w2g, R.o[0] + R.dir[0] * R.te, R.o[1] + R.dir[1] * R.te, R.o[2] + R.dir[2] * R.te, b);
+      tsdf_affine(w2g.m, R.o[0] + R.dir[0] * R.t0, R.o[1] + R.dir[1] * R.t0, R.o[2] + R.dir[2] * R.t0, a);
+      tsdf_affine(w2g.m, R.o[0] + R.dir[0] * R.te, R.o[1] + R.dir[1] * R.te, R.o[2] + R.dir[2] * R.te, b);
       int l[3], h[3];
       bool hits = true;
 #pragma unroll
@@ -198,8 +171,8 @@ __global__ __launch_bounds__(256) void k_points_walk(const float *__restrict__ p
                                                     const float *__restrict__ origins,
                                                     const int32_t *__restrict__ origin_id,
                                                     const uint8_t *__restrict__ colors, int channels, int64_t nrays,
-                                                    int norigins, const int64_t *__restrict__ offsets, PtsAffine w2g,
-                                                    PtsAffine g2w, PtsObb obb, PtsGrid g, PtsBox box,
+                                                    int norigins, const int64_t *__restrict__ offsets, TsdfAffine w2g,
+                                                    TsdfAffine g2w, TsdfObb obb, PtsGrid g, PtsBox box,
                                                     unsigned long long *__restrict__ acc_s,
                                                     unsigned long long *__restrict__ acc_wf,
                                                     unsigned long long *__restrict__ acc_c) {
@@ -224,7 +197,7 @@ __global__ __launch_bounds__(256) void k_points_walk(const float *__restrict__ p
     pts_sample_voxel(R, w2g, half, n, v);
     if (!(v[0] >= 0.f && v[0] < (float)g.dx && v[1] >= 0.f && v[1] < (float)g.dy && v[2] >= 0.f && v[2] < (float)g.dz))
       continue;
-    if (obb.on && !pts_obb_contains(obb, v[0], v[1], v[2])) continue;
+    if (obb.on && !tsdf_obb_contains(obb, v[0], v[1], v[2])) continue;
     if (n > 0) {
       float u[3];
       pts_sample_voxel(R, w2g, half, n - 1, u);
@@ -236,13 +209,12 @@ __global__ __launch_bounds__(256) void k_points_walk(const float *__restrict__ p
     if (bi < 0 || bi >= box.n[0] || bj < 0 || bj >= box.n[1] || bk < 0 || bk >= box.n[2]) continue;
     const int64_t idx = ((int64_t)bk * box.n[1] + bj) * box.n[0] + bi;
     float c[3];
-    pts_affine(g2w, v[0], v[1], v[2], c);
+    tsdf_affine(g2w.m, v[0], v[1], v[2], c);
     const float pz = ((c[0] - R.o[0]) * R.dir[0] + (c[1] - R.o[1]) * R.dir[1]) + (c[2] - R.o[2]) * R.dir[2];
     unsigned long long wf = pz < R.d ? (1ull << 32) : 0ull;
     const float sd0 = R.d - pz;
     if (sd0 > -R.trunc) {
-      const float sd = sd0 >= 0.f ? fminf(R.trunc, sd0) : fmaxf(-R.trunc, sd0);
-      const int q = (int)roundf(__fdiv_rn(sd, g.vs) * 4096.0f);
+      const int q = (int)roundf(__fdiv_rn(tsdf_clamp_sd(sd0, R.trunc), g.vs) * 4096.0f);
       atomicAdd(&acc_s[idx], (unsigned long long)((long long)q * R.wi));     // two's complement: a signed sum
       wf += (unsigned long long)R.wi;
       if constexpr (COLOR) {
@@ -268,6 +240,7 @@ __global__ __launch_bounds__(256) void k_points_fold(float *__restrict__ sdf, ui
                                                     int dy, float vs, PtsBox box, const long long *__restrict__ acc_s,
                                                     const unsigned long long *__restrict__ acc_wf,
                                                     const unsigned long long *__restrict__ acc_c) {
+  const TsdfVol vol{sdf, weight, freec, color};
   const int64_t nb = (int64_t)box.n[0] * box.n[1] * box.n[2];
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x; b < nb; b += stride) {
@@ -276,37 +249,19 @@ __global__ __launch_bounds__(256) void k_points_fold(float *__restrict__ sdf, ui
     const int i = box.lo[0] + (int)(b - row * box.n[0]);
     const int j = box.lo[1] + (int)(row % box.n[1]), k = box.lo[2] + (int)(row / box.n[1]);
     const int64_t v = ((int64_t)k * dy + j) * dx + i;
-    const uint32_t W = (uint32_t)wf, fc = (uint32_t)(wf >> 32);
-    if (fc) freec[v] = (int32_t)((uint32_t)freec[v] + fc);
-    if (W) {
-      const float obs = (float)((double)acc_s[b] / ((double)W * 4096.0)) * vs;
-      const int w = weight[v], wu = (int)min(W, 255u);
-      sdf[v] = w == 0 ? obs : __fdiv_rn(sdf[v] * (float)w + obs * (float)wu, (float)w + (float)wu);
-      weight[v] = (uint8_t)min(w + wu, 255);
-    }
+    const uint32_t W = (uint32_t)wf;
+    tsdf_fold_free(vol, v, (uint32_t)(wf >> 32));
+    if (W) tsdf_fold_geometry(vol, v, (float)((double)acc_s[b] / ((double)W * 4096.0)) * vs, (int)min(W, 255u));
     if constexpr (COLOR) {
       const unsigned long long cw = acc_c[4 * b + 3];
       if (cw) {
-        const uint2 old = color[v];
-        uint32_t q[3] = {old.x & 0xFFFFu, old.x >> 16, old.y & 0xFFFFu};
-        const uint32_t wc = old.y >> 16, wcu = (uint32_t)(cw < 255ull ? cw : 255ull);
+        uint32_t ci[3];                                                                // the call's mean, 8.8
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const uint32_t ci = (uint32_t)((256ull * acc_c[4 * b + c] + cw / 2) / cw);   // the call's mean, 8.8
-          q[c] = wc == 0 ? ci : (q[c] * wc + ci * wcu + (wc + wcu) / 2) / (wc + wcu);
-        }
-        color[v] = make_uint2(q[0] | q[1] << 16, q[2] | min(wc + wcu, 255u) << 16);
+        for (int c = 0; c < 3; ++c) ci[c] = (uint32_t)((256ull * acc_c[4 * b + c] + cw / 2) / cw);
+        tsdf_fold_color(vol, v, ci, (uint32_t)(cw < 255ull ? cw : 255ull));
       }
     }
   }
-}
-
-int pts_affine_arg(const float *host12, PtsAffine &a) {
-  for (int c = 0; c < 12; ++c) {
-    if (!isfinite(host12[c])) return 0;
-    a.m[c] = host12[c];
-  }
-  return 1;
 }
 
 int pts_box_arg(const int32_t *b, int dx, int dy, int dz, PtsBox &box) {
@@ -328,8 +283,8 @@ SGNN_EXPORT int sgnn_points_count(const float *points, const float *origins, con
   SGNN_CHECK_ARG(nrays >= 0 && nrays <= SGNN_POINTS_MAX_RAYS && norigins >= 1 && dx >= 1 && dy >= 1 && dz >= 1);
   SGNN_CHECK_ARG(voxel_size > 0.f && depth_max >= depth_min && isfinite(depth_max) && isfinite(depth_min));
   SGNN_CHECK_ARG(box && world2grid);
-  PtsAffine w2g;
-  SGNN_CHECK_ARG(pts_affine_arg(world2grid, w2g));
+  TsdfAffine w2g;
+  SGNN_CHECK_ARG(tsdf_affine_arg(world2grid, w2g));
   SGNN_LAUNCH(k_points_box_init, dim3(1), dim3(64), 0, (hipStream_t)stream, box);
   SGNN_CHECK_LAUNCH();
   if (nrays == 0) return SGNN_OK;
@@ -354,32 +309,19 @@ SGNN_EXPORT int sgnn_points_walk(const float *points, const float *origins, cons
   if (nrays == 0 || max_samples == 0) return SGNN_OK;
   SGNN_CHECK_ARG(points && origins && offsets && world2grid && grid2world && box && acc_s && acc_wf);
   SGNN_CHECK_ARG(((uintptr_t)acc_s & 7) == 0 && ((uintptr_t)acc_wf & 7) == 0 && ((uintptr_t)acc_c & 7) == 0);
-  PtsAffine w2g, g2w;
+  TsdfAffine w2g, g2w;
   PtsBox b;
-  SGNN_CHECK_ARG(pts_affine_arg(world2grid, w2g) && pts_affine_arg(grid2world, g2w));
+  SGNN_CHECK_ARG(tsdf_affine_arg(world2grid, w2g) && tsdf_affine_arg(grid2world, g2w));
   SGNN_CHECK_ARG(pts_box_arg(box, dx, dy, dz, b));
-  PtsObb o{};
-  if (obb) {
-    o.on = 1;
-    for (int c = 0; c < 3; ++c) o.a[c] = obb[c];
-    for (int k = 0; k < 3; ++k) {
-      for (int c = 0; c < 3; ++c) o.e[k][c] = obb[3 + 3 * k + c];
-      o.ee[k] = (o.e[k][0] * o.e[k][0] + o.e[k][1] * o.e[k][1]) + o.e[k][2] * o.e[k][2];
-    }
-  }
+  const TsdfObb o = tsdf_obb_arg(obb);
   const PtsGrid g{dx, dy, dz, voxel_size, depth_min, depth_max, carve != 0};
   // the number of samples is on the device (offsets[nrays]); max_samples, the caller's bound on it, only sizes the grid
   const dim3 grid(sgnn_grid_for(max_samples, 256, 8192));
   unsigned long long *s = reinterpret_cast<unsigned long long *>(acc_s);
   unsigned long long *wf = reinterpret_cast<unsigned long long *>(acc_wf);
   unsigned long long *c = reinterpret_cast<unsigned long long *>(acc_c);
-  if (colors) {
-    SGNN_LAUNCH(k_points_walk<true>, grid, dim3(256), 0, (hipStream_t)stream, points, origins, origin_id, colors,
-                channels, nrays, norigins, offsets, w2g, g2w, o, g, b, s, wf, c);
-  } else {
-    SGNN_LAUNCH(k_points_walk<false>, grid, dim3(256), 0, (hipStream_t)stream, points, origins, origin_id, colors,
-                channels, nrays, norigins, offsets, w2g, g2w, o, g, b, s, wf, c);
-  }
+  SGNN_LAUNCH(colors ? k_points_walk<true> : k_points_walk<false>, grid, dim3(256), 0, (hipStream_t)stream, points,
+              origins, origin_id, colors, channels, nrays, norigins, offsets, w2g, g2w, o, g, b, s, wf, c);
   SGNN_CHECK_LAUNCH();
   return SGNN_OK;
 }
@@ -388,22 +330,18 @@ SGNN_EXPORT int sgnn_points_fold(float *sdf, uint8_t *weight, int32_t *free_ctr,
                                  int dz, float voxel_size, const int32_t *box, const int64_t *acc_s,
                                  const uint64_t *acc_wf, const uint64_t *acc_c, sgnn_stream_t stream) {
   SGNN_CHECK_ARG(dx >= 1 && dy >= 1 && dz >= 1 && voxel_size > 0.f);
-  SGNN_CHECK_ARG(sdf && weight && free_ctr && box && acc_s && acc_wf && (color == nullptr) == (acc_c == nullptr));
-  SGNN_CHECK_ARG(((uintptr_t)color & 7) == 0 && ((uintptr_t)acc_s & 7) == 0 && ((uintptr_t)acc_wf & 7) == 0 &&
-                 ((uintptr_t)acc_c & 7) == 0);
+  TsdfVol vol;
+  SGNN_CHECK_ARG(tsdf_vol_arg(sdf, weight, free_ctr, color, vol) && box && acc_s && acc_wf);
+  SGNN_CHECK_ARG((color == nullptr) == (acc_c == nullptr));
+  SGNN_CHECK_ARG(((uintptr_t)acc_s & 7) == 0 && ((uintptr_t)acc_wf & 7) == 0 && ((uintptr_t)acc_c & 7) == 0);
   PtsBox b;
   SGNN_CHECK_ARG(pts_box_arg(box, dx, dy, dz, b));
   const dim3 grid(sgnn_grid_for((int64_t)b.n[0] * b.n[1] * b.n[2], 256, 8192));
   const long long *s = reinterpret_cast<const long long *>(acc_s);
   const unsigned long long *wf = reinterpret_cast<const unsigned long long *>(acc_wf);
   const unsigned long long *c = reinterpret_cast<const unsigned long long *>(acc_c);
-  if (color) {
-    SGNN_LAUNCH(k_points_fold<true>, grid, dim3(256), 0, (hipStream_t)stream, sdf, weight, free_ctr,
-                reinterpret_cast<uint2 *>(color), dx, dy, voxel_size, b, s, wf, c);
-  } else {
-    SGNN_LAUNCH(k_points_fold<false>, grid, dim3(256), 0, (hipStream_t)stream, sdf, weight, free_ctr, (uint2 *)nullptr,
-                dx, dy, voxel_size, b, s, wf, c);
-  }
+  SGNN_LAUNCH(color ? k_points_fold<true> : k_points_fold<false>, grid, dim3(256), 0, (hipStream_t)stream, vol.sdf,
+              vol.weight, vol.freec, vol.color, dx, dy, voxel_size, b, s, wf, c);
   SGNN_CHECK_LAUNCH();
   return SGNN_OK;
 }

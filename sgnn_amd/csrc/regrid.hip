@@ -14,29 +14,23 @@
 // Block skip: the 8 corners of the block's destination box go through A; if their box, padded by one voxel and by a
 // bound on the fp32 error of the map (RgMap::pad, formed on the host), misses the source grid on some axis, rules
 // Q.3 - Q.6 fix every voxel of the block as unseen: store mode writes that, fold mode returns before any load.
-// No LDS, no atomics, plain vector loads and stores; the colour record moves as one 8-byte access.
+// No LDS, no atomics, plain vector loads and stores; the colour record moves as one 8-byte access.  The volume's four
+// pointers, the affine row and the fold of rule Q.8 are those of tsdf.h: merge folds exactly as points.hip does.
 //
 // Built with -ffp-contract=off (Makefile): every product and sum below is rounded on its own.
 #include <math.h>
 #include "common.h"
+#include "tsdf.h"
 
 namespace {
 
 struct RgMap {
-  float m[12];    // rows 0..2 of A, row-major
+  TsdfAffine A;   // rows 0..2 of A
   float pad[3];   // per source axis: 1 + a bound on the fp32 error of A.(i, j, k, 1) over the destination grid
 };
 
 struct RgDims {
   int x, y, z;
-};
-
-// the state of one volume; color is NULL where the template says so
-struct RgVol {
-  float *sdf;
-  uint8_t *weight;
-  int32_t *freec;
-  uint2 *color;
 };
 
 template <int SHAPE>
@@ -70,11 +64,6 @@ struct RgShape<2> {   // wave 64 x 1 x 1, block 64 x 4 x 1: the row-major baseli
   }
 };
 
-// ((m0 i + m1 j) + m2 k) + m3, the order of fusion._affine
-__device__ __forceinline__ float rg_row(const RgMap &a, int r, float i, float j, float k) {
-  return ((a.m[4 * r] * i + a.m[4 * r + 1] * j) + a.m[4 * r + 2] * k) + a.m[4 * r + 3];
-}
-
 // l(p, q, a) of rule Q.5; l(p, q, 0) = p by definition (p + 0 (q - p) would turn -0 into +0)
 __device__ __forceinline__ float rg_lerp(float p, float q, float a) { return a == 0.f ? p : p + a * (q - p); }
 
@@ -89,8 +78,8 @@ __device__ __forceinline__ bool rg_block_misses(const RgMap &a, const RgDims &s,
     bool finite = true;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-      const float g = rg_row(a, r, (float)((c & 1) ? hi[0] : lo[0]), (float)((c & 2) ? hi[1] : lo[1]),
-                             (float)((c & 4) ? hi[2] : lo[2]));
+      const float g = tsdf_affine_row(a.A.m, r, (float)((c & 1) ? hi[0] : lo[0]), (float)((c & 2) ? hi[1] : lo[1]),
+                                      (float)((c & 4) ? hi[2] : lo[2]));
       finite = finite && isfinite(g);
       mn = fminf(mn, g);
       mx = fmaxf(mx, g);
@@ -101,7 +90,7 @@ __device__ __forceinline__ bool rg_block_misses(const RgMap &a, const RgDims &s,
 }
 
 template <bool COLOR, bool LINEAR, bool FOLD, int SHAPE>
-__global__ __launch_bounds__(256) void k_regrid(RgVol src, RgDims s, RgMap a, RgVol dst, RgDims d, int skip) {
+__global__ __launch_bounds__(256) void k_regrid(TsdfVol src, RgDims s, RgMap a, TsdfVol dst, RgDims d, int skip) {
   using S = RgShape<SHAPE>;
   int lx, ly, lz;
   S::lane(threadIdx.x, lx, ly, lz);
@@ -127,7 +116,8 @@ __global__ __launch_bounds__(256) void k_regrid(RgVol src, RgDims s, RgMap a, Rg
 
   // rule 1: the voxel's position in source voxel coordinates; rule 3: its nearest voxel
   const float fi = (float)i, fj = (float)j, fk = (float)k;
-  const float g[3] = {rg_row(a, 0, fi, fj, fk), rg_row(a, 1, fi, fj, fk), rg_row(a, 2, fi, fj, fk)};
+  float g[3];
+  tsdf_affine(a.A.m, fi, fj, fk, g);
   const float sd[3] = {(float)(s.x - 1), (float)(s.y - 1), (float)(s.z - 1)};
   const float r[3] = {roundf(g[0]), roundf(g[1]), roundf(g[2])};
   const bool r_in = r[0] >= 0.f && r[0] <= sd[0] && r[1] >= 0.f && r[1] <= sd[1] && r[2] >= 0.f && r[2] <= sd[2];
@@ -187,33 +177,17 @@ __global__ __launch_bounds__(256) void k_regrid(RgVol src, RgDims s, RgMap a, Rg
     if (COLOR) dst.color[v] = c2;
     return;
   }
-  // rule 8
-  if (f2 != 0) dst.freec[v] = (int32_t)((uint32_t)dst.freec[v] + (uint32_t)f2);
-  if (w2 == 0) return;
-  const int w1 = dst.weight[v];
-  if (w1 == 0) {
-    dst.sdf[v] = s2;
-    dst.weight[v] = (uint8_t)w2;
-  } else {
-    dst.sdf[v] = __fdiv_rn(dst.sdf[v] * (float)w1 + s2 * (float)w2, (float)w1 + (float)w2);
-    dst.weight[v] = (uint8_t)min(w1 + w2, 255);
-  }
+  // rule 8: the sample is one observation of the voxel; a sample that is not valid has w2 == 0 and no colour
+  tsdf_fold_free(dst, v, (uint32_t)f2);
+  tsdf_fold_geometry(dst, v, s2, w2);
   if (COLOR) {
-    const uint32_t wcu = c2.y >> 16;
-    if (wcu) {
-      const uint2 old = dst.color[v];
-      uint32_t q[3] = {old.x & 0xFFFFu, old.x >> 16, old.y & 0xFFFFu};
-      const uint32_t ci[3] = {c2.x & 0xFFFFu, c2.x >> 16, c2.y & 0xFFFFu};
-      const uint32_t wc = old.y >> 16;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) q[c] = wc == 0 ? ci[c] : (q[c] * wc + ci[c] * wcu + (wc + wcu) / 2) / (wc + wcu);
-      dst.color[v] = make_uint2(q[0] | q[1] << 16, q[2] | min(wc + wcu, 255u) << 16);
-    }
+    const TsdfColor c = tsdf_color_unpack(c2);
+    tsdf_fold_color(dst, v, c.q, c.w);
   }
 }
 
 template <bool COLOR, bool LINEAR, bool FOLD, int SHAPE>
-void rg_launch_shape(const RgVol &src, const RgDims &s, const RgMap &a, const RgVol &dst, const RgDims &d, int skip,
+void rg_launch_shape(const TsdfVol &src, const RgDims &s, const RgMap &a, const TsdfVol &dst, const RgDims &d, int skip,
                      hipStream_t stream) {
   using S = RgShape<SHAPE>;
   const dim3 grid((d.x + S::BX - 1) / S::BX, (d.y + S::BY - 1) / S::BY, (d.z + S::BZ - 1) / S::BZ);
@@ -221,7 +195,7 @@ void rg_launch_shape(const RgVol &src, const RgDims &s, const RgMap &a, const Rg
 }
 
 template <bool COLOR, bool LINEAR, bool FOLD>
-void rg_launch_mode(int shape, const RgVol &src, const RgDims &s, const RgMap &a, const RgVol &dst, const RgDims &d,
+void rg_launch_mode(int shape, const TsdfVol &src, const RgDims &s, const RgMap &a, const TsdfVol &dst, const RgDims &d,
                     int skip, hipStream_t stream) {
   if (shape == 0) rg_launch_shape<COLOR, LINEAR, FOLD, 0>(src, s, a, dst, d, skip, stream);
   else if (shape == 1) rg_launch_shape<COLOR, LINEAR, FOLD, 1>(src, s, a, dst, d, skip, stream);
@@ -229,7 +203,7 @@ void rg_launch_mode(int shape, const RgVol &src, const RgDims &s, const RgMap &a
 }
 
 template <bool FOLD>
-void rg_launch(bool color, bool linear, int shape, const RgVol &src, const RgDims &s, const RgMap &a, const RgVol &dst,
+void rg_launch(bool color, bool linear, int shape, const TsdfVol &src, const RgDims &s, const RgMap &a, const TsdfVol &dst,
                const RgDims &d, int skip, hipStream_t stream) {
   if (color) {
     if (linear) rg_launch_mode<true, true, FOLD>(shape, src, s, a, dst, d, skip, stream);
@@ -246,13 +220,11 @@ bool rg_dims_ok(int x, int y, int z) {
 
 // A and, per source axis, 1 + 16 ulp-halves of the largest sum of magnitudes the row can reach on the destination grid
 int rg_map_arg(const float *host12, const RgDims &d, RgMap &a) {
-  for (int c = 0; c < 12; ++c) {
-    if (!isfinite(host12[c])) return 0;
-    a.m[c] = host12[c];
-  }
+  if (!tsdf_affine_arg(host12, a.A)) return 0;
+  const float *m = a.A.m;
   for (int r = 0; r < 3; ++r) {
-    const double sum = fabs((double)a.m[4 * r]) * (d.x - 1) + fabs((double)a.m[4 * r + 1]) * (d.y - 1) +
-                       fabs((double)a.m[4 * r + 2]) * (d.z - 1) + fabs((double)a.m[4 * r + 3]);
+    const double sum = fabs((double)m[4 * r]) * (d.x - 1) + fabs((double)m[4 * r + 1]) * (d.y - 1) +
+                       fabs((double)m[4 * r + 2]) * (d.z - 1) + fabs((double)m[4 * r + 3]);
     const double pad = 1.0 + 16.0 * sum * 5.9604644775390625e-08;   // 2^-24
     if (!(pad < 1e30)) return 0;
     a.pad[r] = (float)(pad * (1.0 + 1e-6));
@@ -262,43 +234,41 @@ int rg_map_arg(const float *host12, const RgDims &d, RgMap &a) {
 
 }  // namespace
 
+// the one host side of both entry points; the two differ in the colour rule and the template argument only
+static int regrid(bool fold, const float *src_sdf, const uint8_t *src_weight, const int32_t *src_free,
+                  const uint16_t *src_color, int sdx, int sdy, int sdz, const float *map, int linear, int skip,
+                  int shape, float *dst_sdf, uint8_t *dst_weight, int32_t *dst_free, uint16_t *dst_color, int ddx,
+                  int ddy, int ddz, sgnn_stream_t stream) {
+  SGNN_CHECK_ARG(rg_dims_ok(sdx, sdy, sdz) && rg_dims_ok(ddx, ddy, ddz) && shape >= 0 && shape <= 2);
+  TsdfVol src, dst;
+  SGNN_CHECK_ARG(tsdf_vol_arg(src_sdf, src_weight, src_free, src_color, src) && map);
+  SGNN_CHECK_ARG(tsdf_vol_arg(dst_sdf, dst_weight, dst_free, dst_color, dst));
+  if (!fold) SGNN_CHECK_ARG((src_color == nullptr) == (dst_color == nullptr));   // store: colour on both or on neither
+  SGNN_CHECK_ARG(dst_sdf != src_sdf && dst_weight != src_weight && dst_free != src_free);
+  const RgDims s{sdx, sdy, sdz}, d{ddx, ddy, ddz};
+  RgMap a;
+  SGNN_CHECK_ARG(rg_map_arg(map, d, a));
+  const bool color = src.color != nullptr && dst.color != nullptr;   // fold (rule 8): only where both volumes carry it
+  if (!color) src.color = dst.color = nullptr;
+  if (fold) rg_launch<true>(color, linear != 0, shape, src, s, a, dst, d, skip != 0, (hipStream_t)stream);
+  else rg_launch<false>(color, linear != 0, shape, src, s, a, dst, d, skip != 0, (hipStream_t)stream);
+  SGNN_CHECK_LAUNCH();
+  return SGNN_OK;
+}
+
 SGNN_EXPORT int sgnn_regrid_resample(const float *src_sdf, const uint8_t *src_weight, const int32_t *src_free,
                                      const uint16_t *src_color, int sdx, int sdy, int sdz, const float *map,
                                      int linear, int skip, int shape, float *dst_sdf, uint8_t *dst_weight,
                                      int32_t *dst_free, uint16_t *dst_color, int ddx, int ddy, int ddz,
                                      sgnn_stream_t stream) {
-  SGNN_CHECK_ARG(rg_dims_ok(sdx, sdy, sdz) && rg_dims_ok(ddx, ddy, ddz) && shape >= 0 && shape <= 2);
-  SGNN_CHECK_ARG(src_sdf && src_weight && src_free && dst_sdf && dst_weight && dst_free && map);
-  SGNN_CHECK_ARG((src_color == nullptr) == (dst_color == nullptr));
-  SGNN_CHECK_ARG(((uintptr_t)src_color & 7) == 0 && ((uintptr_t)dst_color & 7) == 0);
-  SGNN_CHECK_ARG(dst_sdf != src_sdf && dst_weight != src_weight && dst_free != src_free);
-  const RgDims s{sdx, sdy, sdz}, d{ddx, ddy, ddz};
-  RgMap a;
-  SGNN_CHECK_ARG(rg_map_arg(map, d, a));
-  const RgVol src{const_cast<float *>(src_sdf), const_cast<uint8_t *>(src_weight), const_cast<int32_t *>(src_free),
-                  reinterpret_cast<uint2 *>(const_cast<uint16_t *>(src_color))};
-  const RgVol dst{dst_sdf, dst_weight, dst_free, reinterpret_cast<uint2 *>(dst_color)};
-  rg_launch<false>(src_color != nullptr, linear != 0, shape, src, s, a, dst, d, skip != 0, (hipStream_t)stream);
-  SGNN_CHECK_LAUNCH();
-  return SGNN_OK;
+  return regrid(false, src_sdf, src_weight, src_free, src_color, sdx, sdy, sdz, map, linear, skip, shape, dst_sdf,
+                dst_weight, dst_free, dst_color, ddx, ddy, ddz, stream);
 }
 
 SGNN_EXPORT int sgnn_regrid_merge(const float *src_sdf, const uint8_t *src_weight, const int32_t *src_free,
                                   const uint16_t *src_color, int sdx, int sdy, int sdz, const float *map, int linear,
                                   int skip, int shape, float *dst_sdf, uint8_t *dst_weight, int32_t *dst_free,
                                   uint16_t *dst_color, int ddx, int ddy, int ddz, sgnn_stream_t stream) {
-  SGNN_CHECK_ARG(rg_dims_ok(sdx, sdy, sdz) && rg_dims_ok(ddx, ddy, ddz) && shape >= 0 && shape <= 2);
-  SGNN_CHECK_ARG(src_sdf && src_weight && src_free && dst_sdf && dst_weight && dst_free && map);
-  SGNN_CHECK_ARG(((uintptr_t)src_color & 7) == 0 && ((uintptr_t)dst_color & 7) == 0);
-  SGNN_CHECK_ARG(dst_sdf != src_sdf && dst_weight != src_weight && dst_free != src_free);
-  const RgDims s{sdx, sdy, sdz}, d{ddx, ddy, ddz};
-  RgMap a;
-  SGNN_CHECK_ARG(rg_map_arg(map, d, a));
-  const bool color = src_color != nullptr && dst_color != nullptr;   // rule 8: only where both volumes carry it
-  const RgVol src{const_cast<float *>(src_sdf), const_cast<uint8_t *>(src_weight), const_cast<int32_t *>(src_free),
-                  color ? reinterpret_cast<uint2 *>(const_cast<uint16_t *>(src_color)) : nullptr};
-  const RgVol dst{dst_sdf, dst_weight, dst_free, color ? reinterpret_cast<uint2 *>(dst_color) : nullptr};
-  rg_launch<true>(color, linear != 0, shape, src, s, a, dst, d, skip != 0, (hipStream_t)stream);
-  SGNN_CHECK_LAUNCH();
-  return SGNN_OK;
+  return regrid(true, src_sdf, src_weight, src_free, src_color, sdx, sdy, sdz, map, linear, skip, shape, dst_sdf,
+                dst_weight, dst_free, dst_color, ddx, ddy, ddz, stream);
 }

@@ -23,6 +23,7 @@
 #include <math.h>
 #include <type_traits>
 #include "common.h"
+#include "tsdf.h"   // the affine row of transform()
 
 namespace {
 
@@ -58,11 +59,7 @@ struct Setup {
 };
 
 __device__ __forceinline__ Vec3 transform(const float *m, float x, float y, float z) {
-  Vec3 p;
-  p.x = ((m[0] * x + m[1] * y) + m[2] * z) + m[3];
-  p.y = ((m[4] * x + m[5] * y) + m[6] * z) + m[7];
-  p.z = ((m[8] * x + m[9] * y) + m[10] * z) + m[11];
-  return p;
+  return Vec3{tsdf_affine_row(m, 0, x, y, z), tsdf_affine_row(m, 1, x, y, z), tsdf_affine_row(m, 2, x, y, z)};
 }
 
 // the point where edge a -> b meets z = zc, always from the kept end a towards the dropped end b

@@ -22,6 +22,7 @@
 #include "box_lists.h"  // the brick walk of k_vox_bricks, shared with meshdist.hip
 #include "first_table.h"
 #include "tri_dist.h"
+#include "tsdf.h"       // the affine row of k_vox_grid_coords
 
 namespace {
 
@@ -60,18 +61,13 @@ __device__ __forceinline__ bool vox_range(float lo, float hi, int n, int &i0, in
   return true;
 }
 
-struct Affine {
-  float m[12];
-};
-
-__global__ __launch_bounds__(256) void k_vox_grid_coords(const float *__restrict__ verts, int64_t nv, Affine w2g,
+__global__ __launch_bounds__(256) void k_vox_grid_coords(const float *__restrict__ verts, int64_t nv, TsdfAffine w2g,
                                                         float *__restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= nv) return;
   const float x = verts[i * 3], y = verts[i * 3 + 1], z = verts[i * 3 + 2];
 #pragma unroll
-  for (int r = 0; r < 3; ++r)
-    out[i * 3 + r] = ((w2g.m[4 * r] * x + w2g.m[4 * r + 1] * y) + w2g.m[4 * r + 2] * z) + w2g.m[4 * r + 3];
+  for (int r = 0; r < 3; ++r) out[i * 3 + r] = tsdf_affine_row(w2g.m, r, x, y, z);
 }
 
 template <bool FILL>
@@ -290,7 +286,7 @@ SGNN_EXPORT int sgnn_vox_grid_coords(const float *verts, int64_t nv, const float
   SGNN_CHECK_ARG(nv >= 0 && nv < ((int64_t)1 << 31) && world2grid);
   if (nv == 0) return SGNN_OK;
   SGNN_CHECK_ARG(verts && out);
-  Affine a;
+  TsdfAffine a;
   for (int k = 0; k < 12; ++k) a.m[k] = world2grid[k];
   SGNN_LAUNCH(k_vox_grid_coords, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, (hipStream_t)stream, verts, nv, a, out);
   SGNN_CHECK_LAUNCH();

@@ -173,6 +173,14 @@ def obb_contains(obb, q):
 # ---------------------------------------------------------------------------------------------------------
 # the volume
 # ---------------------------------------------------------------------------------------------------------
+def check_dims(dims_xyz):
+    """The limits of a volume's dims, before a device is needed -> the dims as a tuple of ints."""
+    dims = tuple(int(d) for d in dims_xyz)
+    if len(dims) != 3 or min(dims) < 1 or max(dims) > 65535 or dims[0] * dims[1] * dims[2] >= 2 ** 31:
+        raise ValueError('unsupported volume dimensions %s' % (dims,))
+    return dims
+
+
 class TSDFVolume(object):
     """A dense truncated signed-distance volume on the device, (dz, dy, dx) like the readers' arrays.
 
@@ -185,9 +193,7 @@ class TSDFVolume(object):
                  color=False):
         self.device = _device(device)
         self.dims_xyz = tuple(int(d) for d in dims_xyz)
-        dx, dy, dz = self.dims_xyz
-        if min(self.dims_xyz) < 1 or max(self.dims_xyz) > 65535 or dx * dy * dz >= 2 ** 31:
-            raise ValueError('unsupported volume dimensions %s' % (self.dims_xyz,))
+        dx, dy, dz = check_dims(self.dims_xyz)
         self.voxel_size = np.float32(voxel_size)
         self.world2grid = _host(world2grid, np.float32).reshape(4, 4).copy()
         self.depth_min, self.depth_max = np.float32(depth_min), np.float32(depth_max)
@@ -202,6 +208,12 @@ class TSDFVolume(object):
     @property
     def dims_zyx(self):
         return self.dims_xyz[::-1]
+
+    def _state(self, color):
+        """The four pointers every entrance to the volume hands to the library (csrc/tsdf.h, TsdfVol); color False:
+        None for the colour record."""
+        return (self._sdf.data_ptr(), self._weight.data_ptr(), self._free.data_ptr(),
+                self._color.data_ptr() if color else None)
 
     def frame_table(self, intrinsics, cam2world, hw):
         """Host table of sgnn_fuse_frame records for F frames of size hw = (h, w)."""
@@ -248,11 +260,9 @@ class TSDFVolume(object):
         tail = (h, w, dev_table.data_ptr(), nf, int(DEFAULT_CHUNK if chunk is None else chunk),
                 float(self.voxel_size), float(self.depth_min), float(self.depth_max), obb)
         if color is None:
-            _lib.call('sgnn_fuse_integrate', self._sdf.data_ptr(), self._weight.data_ptr(), self._free.data_ptr(), dx,
-                      dy, dz, d.data_ptr(), *tail)
+            _lib.call('sgnn_fuse_integrate', *self._state(False)[:3], dx, dy, dz, d.data_ptr(), *tail)
         else:
-            _lib.call('sgnn_fusecol_integrate', self._sdf.data_ptr(), self._weight.data_ptr(), self._free.data_ptr(),
-                      self._color.data_ptr(), dx, dy, dz, d.data_ptr(), color.data_ptr(), *tail)
+            _lib.call('sgnn_fusecol_integrate', *self._state(True), dx, dy, dz, d.data_ptr(), color.data_ptr(), *tail)
         return self
 
     def sdf(self):

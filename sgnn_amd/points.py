@@ -158,8 +158,7 @@ def walk(vol, pts, org, oid, col, carve, r0, r1, offsets, box, grid2world, acc):
 def fold(vol, box, acc):
     """sgnn_points_fold: the call's accumulators into the volume, one observation per voxel."""
     dx, dy, dz = vol.dims_xyz
-    _lib.call('sgnn_points_fold', vol._sdf.data_ptr(), vol._weight.data_ptr(), vol._free.data_ptr(),
-              None if acc[2] is None else vol._color.data_ptr(), dx, dy, dz, float(vol.voxel_size), box.ctypes.data,
+    _lib.call('sgnn_points_fold', *vol._state(acc[2] is not None), dx, dy, dz, float(vol.voxel_size), box.ctypes.data,
               acc[0].data_ptr(), acc[1].data_ptr(), _lib.ptr(acc[2]))
 
 

@@ -25,14 +25,6 @@ MODES = ('linear', 'nearest')
 _DEFAULT_SHAPE = 2
 
 
-def _check_dims(dims_xyz):
-    """TSDFVolume's own limits, before a device is needed."""
-    dims = tuple(int(d) for d in dims_xyz)
-    if len(dims) != 3 or min(dims) < 1 or max(dims) > 65535 or dims[0] * dims[1] * dims[2] >= 2 ** 31:
-        raise ValueError('unsupported volume dimensions %s' % (dims,))
-    return dims
-
-
 def _matrix(m, what):
     m = _host(m, np.float32)
     if m.size != 16 or not np.isfinite(m).all():
@@ -65,10 +57,6 @@ def _mode(mode):
     if mode not in MODES:
         raise ValueError('mode must be one of %s, got %r' % (MODES, mode))
     return int(mode == 'linear')
-
-
-def _state(v, color):
-    return (v._sdf.data_ptr(), v._weight.data_ptr(), v._free.data_ptr(), v._color.data_ptr() if color else None)
 
 
 def grid_for(vol, world_transform=None, voxel_size=None, pad=0):
@@ -110,7 +98,7 @@ def resample(vol, dims_xyz, world2grid, voxel_size=None, mode='linear', skip=Tru
     depth_min / depth_max are copied, the result has no obb.  mode: 'linear' (rule Q.5) or 'nearest' (rule Q.4).  skip: a
     launch detail, the result does not depend on it.  _shape picks the wave brick for the benchmark and the tests; it is
     not part of the interface and may go."""
-    dims = _check_dims(dims_xyz)
+    dims = fusion.check_dims(dims_xyz)
     linear = _mode(mode)
     a = grid_map(vol.world2grid, world2grid)
     vs = vol.voxel_size if voxel_size is None else np.float32(voxel_size)
@@ -121,8 +109,8 @@ def resample(vol, dims_xyz, world2grid, voxel_size=None, mode='linear', skip=Tru
     out = fusion.TSDFVolume(dims, vs, _matrix(world2grid, 'world2grid'), vol.depth_min, vol.depth_max, device=vol.device,
                             color=color)
     sx, sy, sz = vol.dims_xyz
-    _lib.call('sgnn_regrid_resample', *_state(vol, color), sx, sy, sz, a.ctypes.data, linear, int(bool(skip)),
-              int(_DEFAULT_SHAPE if _shape is None else _shape), *_state(out, color), *dims)
+    _lib.call('sgnn_regrid_resample', *vol._state(color), sx, sy, sz, a.ctypes.data, linear, int(bool(skip)),
+              int(_DEFAULT_SHAPE if _shape is None else _shape), *out._state(color), *dims)
     return out
 
 
@@ -133,16 +121,16 @@ def merge(dst, src, mode='linear', skip=True, _shape=None):
     if dst is src:
         raise ValueError('a volume cannot be merged into itself')
     linear = _mode(mode)
-    _check_dims(dst.dims_xyz)
-    _check_dims(src.dims_xyz)
+    fusion.check_dims(dst.dims_xyz)
+    fusion.check_dims(src.dims_xyz)
     a = grid_map(src.world2grid, dst.world2grid)
     if dst.device != src.device:
         raise ValueError('the volumes are on different devices (%s, %s)' % (dst.device, src.device))
     _lib.require_gpu()
     color = dst._color is not None and src._color is not None
     sx, sy, sz = src.dims_xyz
-    _lib.call('sgnn_regrid_merge', *_state(src, color), sx, sy, sz, a.ctypes.data, linear, int(bool(skip)),
-              int(_DEFAULT_SHAPE if _shape is None else _shape), *_state(dst, color), *dst.dims_xyz)
+    _lib.call('sgnn_regrid_merge', *src._state(color), sx, sy, sz, a.ctypes.data, linear, int(bool(skip)),
+              int(_DEFAULT_SHAPE if _shape is None else _shape), *dst._state(color), *dst.dims_xyz)
     return dst
 
 
@@ -150,7 +138,7 @@ def resample_pyramid(pyr, dims_xyz, world2grid, mode='linear', skip=True):
     """Every level of a fusion.TSDFPyramid on the grid (dims_xyz, world2grid) of its level 0: level k goes to dims
     ceil(d / 2**k) and world2grid_k = level_transform(k) @ world2grid (fp64 from the fp32 matrix, rounded once), the
     way TSDFPyramid forms its levels, with one resample per level; each level keeps its voxel size."""
-    dims = _check_dims(dims_xyz)
+    dims = fusion.check_dims(dims_xyz)
     w2g = _matrix(world2grid, 'world2grid').astype(np.float64)
     _mode(mode)
     levels = [([-(-d // 2 ** k) for d in dims], (fusion.level_transform(k) @ w2g).astype(np.float32))

@@ -149,7 +149,38 @@ def grid_b():
 
 def as_vol(g):
     """A fusion_ref.Grid as a regrid_ref.Vol."""
-    return GR.from_state(g.dims, g.vs, g.w2g, g.sdf, g.weight, g.free)
+    return GR.from_state(g.dims, g.vs, g.w2g, g.sdf, g.weight, g.free, getattr(g, 'color', None))
+
+
+# ---------------------------------------------------------------------------------------------------------
+# one fold, two callers: a cloud fused directly, and fused on an empty volume that is then merged (rules P and Q.8)
+# ---------------------------------------------------------------------------------------------------------
+FOLD_HW = (30, 40)
+FOLD_VOXEL = (16, 18, 12)       # 0.54 m from the eye of pose 2: every ray that ends in it weighs 4
+FOLD_AIMED = 72                 # 72 x 4 = 288 > 255: the call's weight for that voxel saturates
+
+
+@functools.lru_cache(maxsize=None)
+def fold_scene():
+    """The corner of the room of points_scenes on PS.DIMS voxels: two depth frames (poses 1 and 4) that fill the volume
+    first, and a coloured cloud from two origins: every eighth pixel of the frames of poses 2 and 3 (300 rays, a fifth
+    with A == 0) and FOLD_AIMED rays from pose 2 that end inside FOLD_VOXEL.  dict: dims, w2g, depth, k, poses, pts, org,
+    oid, rgba."""
+    import points_ref as PR
+    room = PS.room()
+    k = np.tile(np.array([28.0, 28.0, 19.5, 14.5], F32), (6, 1))
+    depth = RR.render_ref(room['verts'], room['faces'], k, room['poses'], FOLD_HW)
+    pts, org, oid = PR.from_depth(depth[2:4], k[2:4], room['poses'][2:4])
+    pts, oid = pts[::8], oid[::8]
+    rng = np.random.default_rng(17)
+    centre = (np.array(FOLD_VOXEL, np.float64) - room['w2g'][:3, 3]) * float(PS.VS)     # w2g is a scale and a shift
+    aimed = (centre + rng.uniform(-0.3, 0.3, (FOLD_AIMED, 3)) * float(PS.VS)).astype(F32)
+    pts, oid = np.concatenate([pts, aimed]), np.concatenate([oid, np.zeros(FOLD_AIMED, np.int32)])
+    rgba = rng.integers(0, 256, (len(pts), 4), dtype=np.uint8)
+    rgba[:, 3] = np.where(rng.random(len(pts)) < 0.2, 0, 255)
+    sel = [1, 4]
+    return {'dims': PS.DIMS, 'w2g': room['w2g'], 'depth': depth[sel], 'k': k[sel], 'poses': room['poses'][sel],
+            'pts': pts, 'org': org, 'oid': oid, 'rgba': rgba}
 
 
 @functools.lru_cache(maxsize=None)

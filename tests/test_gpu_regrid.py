@@ -16,7 +16,7 @@ import regrid_ref as GR  # noqa: E402
 from test_regrid_ref import (E2E_FACTOR, E2E_MEASURED, MERGE_EXTRA_MEASURED, MERGE_MEASURED, MIN_FAR_VOXELS,  # noqa: E402
                              MIN_VOXELS, RESAMPLE_EXTRA_MEASURED, RESAMPLE_MEASURED, extra_limits, limits)
 
-from sgnn_amd import fusion, marching_cubes as mc, meshdist, regrid, render, voxelize  # noqa: E402
+from sgnn_amd import fusion, marching_cubes as mc, meshdist, points, regrid, render, voxelize  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -177,6 +177,30 @@ def test_merge_twice_is_deterministic_and_pyramids_resample_level_by_level():
         alone = regrid.resample(pyr[k], ld, lw)
         assert level.dims_xyz == ld and np.array_equal(level.world2grid, lw) and level.voxel_size == pyr[k].voxel_size
         assert same(device_state(level), device_state(alone)) and int((level.weight() > 0).sum()) > 0
+
+
+@pytest.mark.parametrize('carve', [True, False])
+def test_a_cloud_fused_directly_and_a_cloud_merged_are_one_fold(carve):
+    """Rules P and Q.8 claim the same fold, and csrc/tsdf.h writes it once: a cloud integrated into V, and the same
+    cloud integrated into an empty volume on V's grid that is then merged into a copy of V, leave the same bits in sdf,
+    weight, free counter and colour record, in both modes (equal world2grid: the identity map, every a == 0).  The
+    scene and what it exercises are checked on the restatements in tests/test_regrid_ref.py; the cloud goes in twice, so
+    the second call meets the colour and the saturated weights of the first."""
+    sc = RC.fold_scene()
+
+    def empty():
+        return fusion.TSDFVolume(sc['dims'], PS.VS, sc['w2g'], color=True)
+    direct = empty().integrate(sc['depth'], sc['k'], sc['poses'])
+    via = {mode: direct.copy() for mode in regrid.MODES}
+    alone = points.integrate(empty(), sc['pts'], sc['org'], sc['oid'], color=sc['rgba'], carve=carve)
+    x, y, z = RC.FOLD_VOXEL
+    assert int(alone.weight()[z, y, x]) == 255 and int((direct.weight() > 0).sum()) > 3000
+    for _ in range(2):
+        points.integrate(direct, sc['pts'], sc['org'], sc['oid'], color=sc['rgba'], carve=carve)
+        for mode, v in via.items():
+            regrid.merge(v, alone, mode=mode)
+            assert same(device_state(v), device_state(direct)), mode
+    assert int((direct.color_weight() == 255).sum()) > 0
 
 
 @functools.lru_cache(maxsize=None)

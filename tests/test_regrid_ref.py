@@ -161,6 +161,33 @@ def test_the_merge_fold_by_hand():
     assert GR.merge(c, b).color is None and c.weight[0, 0].tolist() == [6, 255]
 
 
+@pytest.mark.parametrize('carve', [True, False])
+def test_a_cloud_fused_directly_and_a_cloud_merged_are_one_fold(carve):
+    """Rules P and Q.8 claim the same fold (csrc/tsdf.h writes it once): a cloud integrated into V, and the same cloud
+    integrated into an empty volume on V's grid that is then merged into a copy of V, leave the same bits.  With equal
+    world2grid the map is the identity and every a == 0, so both modes qualify.  The cloud goes in twice: the second
+    call meets the colour and the saturated weights the first one left."""
+    import fusion_ref as FR
+    import points_ref as PR
+    sc = RC.fold_scene()
+    cloud = (sc['pts'], sc['org'], sc['oid'], sc['rgba'], carve)
+    filled = FR.Grid(sc['dims'], PS.VS, sc['w2g']).integrate(sc['depth'], sc['k'], sc['poses'])
+    direct = PR.Volume(sc['dims'], PS.VS, sc['w2g'], color=True)
+    direct.sdf, direct.weight, direct.free = filled.sdf.copy(), filled.weight.copy(), filled.free.copy()
+    via = {mode: RC.as_vol(direct) for mode in ('linear', 'nearest')}
+    alone = PR.integrate(PR.Volume(sc['dims'], PS.VS, sc['w2g'], color=True), *cloud)
+    x, y, z = RC.FOLD_VOXEL
+    assert (filled.weight > 0).sum() > 3000 and ((filled.weight > 0) & (alone.weight > 0)).sum() > 300
+    assert ((filled.weight == 0) & (alone.weight > 0)).sum() > 50 and (alone.color[..., 3] > 0).sum() > 200
+    assert alone.weight[z, y, x] == 255 and alone.free.max() > RC.FOLD_AIMED // 2
+    for _ in range(2):
+        PR.integrate(direct, *cloud)
+        for mode, v in via.items():
+            GR.merge(v, RC.as_vol(alone), mode)
+            assert same(RC.arrays(v), RC.arrays(RC.as_vol(direct))), mode
+    assert direct.weight[z, y, x] == 255 and (direct.color[..., 3] == 255).any()
+
+
 def figures(got, want):
     share, diff, n = PS.cross_route_figures(got.sdf, got.weight, want.sdf, want.weight, PS.VS)
     return n, share, diff

@@ -1,5 +1,5 @@
-"""Host glue shared by the device-side tools (fusion, render, meshdist, raycast, track, marching_cubes,
-components, simplify, voxelize, edt): where an input ends up; the checks and the upload of a triangle mesh (mesh_shape,
+"""Host glue shared by the device-side tools (fusion, render, meshdist, raycast, track, marching_cubes, components,
+simplify, voxelize, edt, chunks, data): where an input ends up; the checks and the upload of a triangle mesh (mesh_shape,
 mesh_upload) and of cameras (camera_shapes, cameras); and the allocate-and-call wrappers of sgnn_meshdist_pack
 (pack_faces), of a count / fill pair of CSR list passes (binned_lists), of the shared mesh entry points
 (csrc/mesh_tables.hip) and of sgnn_compact_mask.  Plumbing only; every helper does what its callers wrote out before.
@@ -99,14 +99,15 @@ def camera_shapes(intrinsics, cam2world):
         raise ValueError('cam2world must be (F, 4, 4), got %s' % (tuple(np.shape(cam2world)),))
 
 
-def compact(mask, n, dev, read=True):
+def compact(mask, n, dev, read=True, ws=None):
     """sgnn_compact_mask: (sel int32, count): sel[:count] = the rows of the uint8 mask (n,) that are set, in order.
-    count is an int, or with read=False the device int64[1], so that the caller can read it back later."""
+    count is an int, or with read=False the device int64[1], so that the caller can read it back later.  ws: a uint8
+    workspace of at least sgnn_compact_ws_bytes(n) that the caller keeps (default: a fresh one)."""
     sel = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
     cnt = torch.zeros(1, dtype=torch.int64, device=dev)
-    wsb = _lib.query('sgnn_compact_ws_bytes', n)
-    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
-    _lib.call('sgnn_compact_mask', _lib.ptr(mask), n, _lib.ptr(sel), _lib.ptr(cnt), _lib.ptr(ws), wsb)
+    if ws is None:
+        ws = torch.empty(max(_lib.query('sgnn_compact_ws_bytes', n), 1), dtype=torch.uint8, device=dev)
+    _lib.call('sgnn_compact_mask', _lib.ptr(mask), n, _lib.ptr(sel), _lib.ptr(cnt), _lib.ptr(ws), ws.numel())
     return sel, (int(cnt.item()) if read else cnt)
 
 

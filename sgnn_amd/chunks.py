@@ -21,7 +21,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, data
+from . import _glue, _lib, data
 
 BRICK = 8            # scoring granularity of sgnn_chunk_score: window origins, strides and extents are multiples of it
 LEVELS = 4           # a .sdfs chunk carries the target at 1x and three hierarchy blocks (1/2, 1/4, 1/8)
@@ -157,10 +157,7 @@ class ChunkCutter(object):
         mask = torch.empty(n, dtype=torch.uint8, device=dev)
         _lib.call('sgnn_chunk_flag', vol.sdf().data_ptr(), dx, dy, dz, dev_o.data_ptr(), nb, cz, cy, cx, self._keep(0),
                   float(self.truncation), vs, mask.data_ptr())
-        sel = torch.empty(n, dtype=torch.int32, device=dev)
-        count = torch.zeros(1, dtype=torch.int64, device=dev)
-        ws = torch.empty(max(int(_lib.query('sgnn_compact_ws_bytes', n)), 1), dtype=torch.uint8, device=dev)
-        _lib.call('sgnn_compact_mask', mask.data_ptr(), n, sel.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel())
+        sel, count = _glue.compact(mask, n, dev, read=False)
         # dense targets while the count travels: one launch per level
         sdf, known = self._dense(self.target[0], 0, dev_o, nb, vs, known=True)
         hierarchy = [self._dense(self.target[k], k, dev_o, nb, vs) for k in (3, 2, 1)]

@@ -28,7 +28,7 @@ import threading
 import numpy as np
 import torch
 
-from . import _lib
+from . import _glue, _lib
 
 KIND_CHUNK, KIND_SCENE, KIND_KNOWN = 0, 1, 2
 HEADER_BYTES = 92
@@ -424,13 +424,9 @@ class DeviceBatchLoader(object):
         n, o_l, o_v, o_s = plan['blocks']['input']
         p_l, p_v, p_s = raw[o_l:].data_ptr(), raw[o_v:].data_ptr(), raw[o_s:].data_ptr()
         mask = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
-        sel = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        count = torch.zeros(1, dtype=torch.int64, device=dev)
         _lib.call('sgnn_io_flag_entries', p_l, p_v, vs.data_ptr(), p_s, nb, n, self.truncation, in_limit,
                   mask.data_ptr())
-        wsb = _lib.query('sgnn_compact_ws_bytes', n)
-        ws = self._workspace(wsb)
-        _lib.call('sgnn_compact_mask', mask.data_ptr(), n, sel.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel())
+        sel, count = _glue.compact(mask, n, dev, read=False, ws=self._workspace(_lib.query('sgnn_compact_ws_bytes', n)))
         locs = torch.empty((n, 4), dtype=torch.int64, device=dev)
         feats = torch.empty((n, 1), dtype=torch.float32, device=dev)
         _lib.call('sgnn_io_emit_entries', p_l, p_v, vs.data_ptr(), p_s, nb, sel.data_ptr(), count.data_ptr(), n,

@@ -8,7 +8,7 @@ from torch.autograd import Function
 
 from .. import _lib
 from .._lib import ptr
-from .metadata import runtime
+from .metadata import runtime, rows_i64
 from .sites import info, attach
 
 import os
@@ -47,6 +47,16 @@ def conv_fwd_raw(x, cin, w, K, table, ld, n_out, cout, flags=0, in_shift=0):
     return y
 
 
+def conv_fwd_ex(x, n_in, cin, w, K, table, ld, n_out, cout, shape, flags, ex):
+    """sgnn_conv_fwd_ex into a fresh output of `shape`.  ex = (kmap, gmap, in_groups, groups, ktotal), the grouped walk
+    of sgnn_hip.h; K counts the offsets of ONE group."""
+    kmap, gmap, in_groups, groups, ktotal = ex
+    y = torch.empty(shape, dtype=torch.float32, device=x.device)
+    _lib.call('sgnn_conv_fwd_ex', ptr(x), n_in, cin, ptr(w), K, ptr(table), ld, n_out, cout, ptr(y), flags, 0, ptr(kmap),
+              ptr(gmap), in_groups, groups, ktotal)
+    return y
+
+
 _SPLIT_SHAPES = {(16, 24), (24, 16), (24, 32), (32, 24), (64, 32), (32, 64), (56, 28), (28, 56)}
 _arange_cache = {}
 
@@ -65,19 +75,27 @@ def conv_fwd_split(x, cin, w, K, table, ld, n_out, cout, flags=0):
     kmap = _arange_cache.get(key)
     if kmap is None:
         kmap = _arange_cache[key] = torch.arange(K, dtype=torch.int32, device=x.device)
-    part = torch.empty(n_out, G * cout, dtype=torch.float32, device=x.device)
-    _lib.call('sgnn_conv_fwd_ex', ptr(x), x.shape[0], cin, ptr(w), K // G, ptr(table), ld, n_out, cout, ptr(part), flags,
-              0, ptr(kmap), None, 1, G, K)
+    part = conv_fwd_ex(x, x.shape[0], cin, w, K // G, table, ld, n_out, cout, (n_out, G * cout), flags,
+                       (kmap, None, 1, G, K))
     return sum_groups_raw(part, cout, n_out, G)
 
 
-def conv_dw_raw(x, cin, dy, cout, table, ld, K, n_out, in_shift=0):
+def conv_dw_raw(x, cin, dy, cout, table, ld, K, n_out, in_shift=0, n_in=None, ex=None):
+    """dW (K, cin, cout) of conv_fwd_raw; n_in: rows of x (default: all of them).  With ex = (kmap, gmap, in_groups,
+    groups, ktotal), of conv_fwd_ex: K offsets per group, dW (groups * K, cin, cout)."""
     rt = runtime(x.device)
-    dw = torch.empty(K, cin, cout, dtype=torch.float32, device=x.device)
-    wsb = _lib.query('sgnn_conv_bwd_weight_ws_bytes', n_out, K, cin, cout)
+    n_in = x.shape[0] if n_in is None else n_in
+    kw = K if ex is None else K * ex[3]
+    dw = torch.empty(kw, cin, cout, dtype=torch.float32, device=x.device)
+    wsb = _lib.query('sgnn_conv_bwd_weight_ws_bytes', n_out, kw, cin, cout)
     ws = rt.workspace(wsb)
-    _lib.call('sgnn_conv_bwd_weight', ptr(x), x.shape[0], cin, ptr(dy), cout, ptr(table), ld, K, n_out, ptr(dw),
-              in_shift, ptr(ws), wsb)
+    if ex is None:
+        _lib.call('sgnn_conv_bwd_weight', ptr(x), n_in, cin, ptr(dy), cout, ptr(table), ld, K, n_out, ptr(dw), in_shift,
+                  ptr(ws), wsb)
+    else:
+        kmap, gmap, in_groups, groups, ktotal = ex
+        _lib.call('sgnn_conv_bwd_weight_ex', ptr(x), n_in, cin, ptr(dy), cout, ptr(table), ld, K, n_out, ptr(dw), in_shift,
+                  ptr(kmap), ptr(gmap), in_groups, groups, ktotal, ptr(ws), wsb)
     return dw
 
 
@@ -142,9 +160,8 @@ class DenseK4S2(Function):
             y = conv_fwd_split(x, cin, weight, 64, lvl.tdown, lvl.ld_c, lvl.n_c, cout, 0)
         elif parity:
             assert x.shape[0] == lvl.n_c
-            y8 = torch.empty(8 * lvl.n_c, cout, dtype=torch.float32, device=x.device)
-            _lib.call('sgnn_conv_fwd_ex', ptr(x), lvl.n_c, cin, ptr(weight), 8, ptr(lvl.nbr27), lvl.ld_c, lvl.n_c, cout,
-                      ptr(y8), 0, 0, ptr(lvl.slots), None, 1, 8, 27)
+            y8 = conv_fwd_ex(x, lvl.n_c, cin, weight, 8, lvl.nbr27, lvl.ld_c, lvl.n_c, cout, (8 * lvl.n_c, cout), 0,
+                             (lvl.slots, None, 1, 8, 27))
             y = gather_rows_raw(y8, cout, lvl.child_of_raster, lvl.n_f)
         else:
             y = conv_fwd_split(x, cin, weight, 64, lvl.tup, lvl.ld_f, lvl.n_f, cout, 0)
@@ -163,9 +180,8 @@ class DenseK4S2(Function):
             if not down:         # coarse side: all 64 taps
                 dx = conv_fwd_split(dy, cout, weight, 64, lvl.tdown, lvl.ld_c, lvl.n_c, cin, CONV_TRANSPOSE_W)
             elif parity:
-                dx8 = torch.empty(8 * lvl.n_c, cin, dtype=torch.float32, device=dy.device)
-                _lib.call('sgnn_conv_fwd_ex', ptr(dy), lvl.n_c, cout, ptr(weight), 8, ptr(lvl.nbr27), lvl.ld_c, lvl.n_c,
-                          cin, ptr(dx8), CONV_TRANSPOSE_W, 0, ptr(lvl.slots), None, 1, 8, 27)
+                dx8 = conv_fwd_ex(dy, lvl.n_c, cout, weight, 8, lvl.nbr27, lvl.ld_c, lvl.n_c, cin, (8 * lvl.n_c, cin),
+                                  CONV_TRANSPOSE_W, (lvl.slots, None, 1, 8, 27))
                 dx = gather_rows_raw(dx8, cin, lvl.child_of_raster, lvl.n_f)
             else:
                 dx = conv_fwd_split(dy, cout, weight, 64, lvl.tup, lvl.ld_f, lvl.n_f, cin, CONV_TRANSPOSE_W)
@@ -174,12 +190,7 @@ class DenseK4S2(Function):
                 dw = conv_dw_raw(x, cin, dy, cout, lvl.tdown, lvl.ld_c, 64, lvl.n_c)
             elif parity:
                 dy8 = gather_rows_raw(dy, cout, lvl.raster_of_child, lvl.n_f)
-                rt = runtime(x.device)
-                dw = torch.empty_like(weight)
-                wsb = _lib.query('sgnn_conv_bwd_weight_ws_bytes', lvl.n_c, 64, cin, cout)
-                ws = rt.workspace(wsb)
-                _lib.call('sgnn_conv_bwd_weight_ex', ptr(x), lvl.n_c, cin, ptr(dy8), cout, ptr(lvl.nbr27), lvl.ld_c, 8,
-                          lvl.n_c, ptr(dw), 0, ptr(lvl.slots), None, 1, 8, 27, ptr(ws), wsb)
+                dw = conv_dw_raw(x, cin, dy8, cout, lvl.nbr27, lvl.ld_c, 8, lvl.n_c, 0, lvl.n_c, (lvl.slots, None, 1, 8, 27))
             else:
                 dw = conv_dw_raw(x, cin, dy, cout, lvl.tup, lvl.ld_f, 64, lvl.n_f)
         return dx, dw, None, None, None
@@ -232,9 +243,7 @@ class ExpandConv(Function):
         f, wc = _f32c(f), _f32c(wc)
         cin, cout = wc.shape[1], wc.shape[2]
         _, S, ST, PAR = expand_maps(f.device)
-        y = torch.empty(8 * n, cout, dtype=torch.float32, device=f.device)
-        _lib.call('sgnn_conv_fwd_ex', ptr(f), n, cin, ptr(wc), 8, ptr(table), ld, n, cout, ptr(y), 0, 0, ptr(S), None,
-                  1, 8, 27)
+        y = conv_fwd_ex(f, n, cin, wc, 8, table, ld, n, cout, (8 * n, cout), 0, (S, None, 1, 8, 27))
         ctx.save_for_backward(f, wc)
         ctx.cfg = (table, ld, n)
         return y
@@ -251,17 +260,11 @@ class ExpandConv(Function):
             # 64 offsets per parent row: cut into G slices that run as conv groups (G x the workgroups, 1/G of the
             # serial offset walk per workgroup), slices added by sgnn_sum_groups — as for the dense bottleneck
             G = EXPAND_DX_SPLIT
-            part = torch.empty(n, G * cin, dtype=torch.float32, device=f.device)
-            _lib.call('sgnn_conv_fwd_ex', ptr(dy), 8 * n, cout, ptr(wc), 64 // G, ptr(table), ld, n, cin, ptr(part),
-                      CONV_TRANSPOSE_W, 0, ptr(ST), ptr(PAR), 8, G, 27)
+            part = conv_fwd_ex(dy, 8 * n, cout, wc, 64 // G, table, ld, n, cin, (n, G * cin), CONV_TRANSPOSE_W,
+                               (ST, PAR, 8, G, 27))
             df = part if G == 1 else sum_groups_raw(part, cin, n, G)
         if ctx.needs_input_grad[1]:
-            rt = runtime(f.device)
-            dwc = torch.empty_like(wc)
-            wsb = _lib.query('sgnn_conv_bwd_weight_ws_bytes', n, 64, cin, cout)
-            ws = rt.workspace(wsb)
-            _lib.call('sgnn_conv_bwd_weight_ex', ptr(f), n, cin, ptr(dy), cout, ptr(table), ld, 8, n, ptr(dwc), 0,
-                      ptr(S), None, 1, 8, 27, ptr(ws), wsb)
+            dwc = conv_dw_raw(f, cin, dy, cout, table, ld, 8, n, 0, n, (S, None, 1, 8, 27))
         return df, dwc, None, None, None
 
 
@@ -327,8 +330,8 @@ class BatchNormLeaky(Function):
         return dx, dgamma, dbeta, None, None, None, None, None, None
 
 
-def gather_rows_raw(src, c, idx, m):
-    dst = torch.empty(m, c, dtype=torch.float32, device=src.device)
+def gather_rows_raw(src, c, idx, m, dtype=torch.float32):
+    dst = torch.empty(m, c, dtype=dtype, device=src.device)
     _lib.call('sgnn_gather_rows', ptr(src), c, ptr(idx), m, ptr(dst))
     return dst
 
@@ -537,49 +540,55 @@ class DenseToSparseFn(Function):
 # ---------------------------------------------------------------------------
 # non-differentiable index helpers
 # ---------------------------------------------------------------------------
+def _compact(rt, n, rows, logits=None, stride=0, coords=None, teacher=None, mask=None, cap=None, locs=None):
+    """One stable compaction of n candidate rows into a fresh sel (int32, `rows` rows), on rt's workspace.  The flags: the
+    uint8 `mask`; or teacher > 0.5 at `coords`, teacher a dense target occupancy volume (B,1,d0,d1,d2); or
+    sigmoid(logits) > 0.5.  cap = (n_cnt, cnt2, K): capacity mode, candidate count, kept counts and overflow status on
+    the device (see compact_capped), else the count goes to rt.state.  locs (with cap): receives coords[sel[r]], r < K."""
+    sel = torch.empty(rows, dtype=torch.int32, device=rt.device)
+    wsb = _lib.query('sgnn_compact_ws_bytes', n)
+    ws = rt.workspace(wsb)
+    if mask is not None:
+        name, head, mid = 'sgnn_compact_mask', (ptr(mask), n), ()
+    elif teacher is None:
+        name, head, mid = 'sgnn_compact_sigmoid', (ptr(logits), stride, n), (() if locs is None else (ptr(coords),))
+    else:
+        B, _, d0, d1, d2 = (int(v) for v in teacher.shape)
+        name, head, mid = 'sgnn_compact_dense', (ptr(coords), n), (ptr(teacher), B, d0, d1, d2)
+    out = (ptr(sel),) if locs is None else (ptr(sel), ptr(locs))
+    if cap is None:
+        _lib.call(name, *head, *mid, *out, ptr(rt.state), ptr(ws), wsb)
+    else:
+        n_cnt, cnt2, K = cap
+        _lib.call(name + ('_cap' if locs is None else '_cap_locs'), *head, ptr(n_cnt), *mid, *out, ptr(cnt2), K,
+                  ptr(rt.status32), ptr(ws), wsb)
+    return sel
+
+
 def compact_sigmoid(logits, stride, n):
     """Stable list of rows with sigmoid(logit) > 0.5 -> (sel int32[count], count).  One host sync."""
     rt = runtime(logits.device)
-    sel = torch.empty(max(n, 1), dtype=torch.int32, device=logits.device)
-    wsb = _lib.query('sgnn_compact_ws_bytes', n)
-    ws = rt.workspace(wsb)
-    _lib.call('sgnn_compact_sigmoid', ptr(logits), stride, n, ptr(sel), ptr(rt.state), ptr(ws), wsb)
+    sel = _compact(rt, n, max(n, 1), logits, stride)
     count = rt.read_count()
     return sel[:count], count
-
-
-def _compact_call(logits, stride, n, coords_all, sel, rt, ws, wsb, teacher):
-    if teacher is None:
-        _lib.call('sgnn_compact_sigmoid', ptr(logits), stride, n, ptr(sel), ptr(rt.state), ptr(ws), wsb)
-    else:       # masks from a dense target occupancy volume (B,1,d0,d1,d2) instead of the predicted logits
-        B, _, d0, d1, d2 = (int(v) for v in teacher.shape)
-        _lib.call('sgnn_compact_dense', ptr(coords_all), n, ptr(teacher), B, d0, d1, d2, ptr(sel), ptr(rt.state), ptr(ws),
-                  wsb)
 
 
 def compact_sigmoid_plan(logits, stride, n, coords_all, depth, teacher=None):
     """compact_sigmoid + the kept rows' coordinates + the stride-2 pyramid (`depth` levels) below them, with ONE host
     read-back for all row counts: the coordinate gather and the pyramid kernels read the kept-row count from device
     memory (sgnn_gather_rows_dn, sgnn_down2_chain).  Returns (sel[:count], count, locs (count,4) int32); when a
-    pyramid was built, `locs` carries it (sites.info(locs).plan) and the next InputLayer adopts it instead of rebuilding."""
+    pyramid was built, `locs` carries it (sites.info(locs).plan) and the next InputLayer adopts it instead of rebuilding.
+    teacher: the masks come from this dense target occupancy volume instead of the predicted logits."""
     from . import metadata as MD
     rt = runtime(logits.device)
     if not MD.CHAIN or depth < 1 or n == 0:
-        if teacher is None:
-            sel, cnt = compact_sigmoid(logits, stride, n)
-        else:
-            sel = torch.empty(max(n, 1), dtype=torch.int32, device=logits.device)
-            wsb = _lib.query('sgnn_compact_ws_bytes', n)
-            _compact_call(logits, stride, n, coords_all, sel, rt, rt.workspace(wsb), wsb, teacher)
-            cnt = rt.read_count()
-            sel = sel[:cnt]
+        sel = _compact(rt, n, max(n, 1), logits, stride, coords_all, teacher)
+        cnt = rt.read_count()
+        sel = sel[:cnt]
         if MD.COUNT_LOG is not None:
             MD.COUNT_LOG.append(('gen', int(cnt), []))
         return sel, cnt, gather_coords(coords_all, sel, cnt)
-    sel = torch.empty(n, dtype=torch.int32, device=logits.device)
-    wsb = _lib.query('sgnn_compact_ws_bytes', n)
-    ws = rt.workspace(wsb)
-    _compact_call(logits, stride, n, coords_all, sel, rt, ws, wsb, teacher)
+    sel = _compact(rt, n, n, logits, stride, coords_all, teacher)
     locs_cap = torch.empty(n, 4, dtype=torch.int32, device=logits.device)
     _lib.call('sgnn_gather_rows_dn', ptr(coords_all), 4, ptr(sel), ptr(rt.state), n, ptr(locs_cap))
     _inherit_bounds(locs_cap, coords_all)
@@ -604,28 +613,12 @@ def compact_capped(logits, stride, n_all, coords_all, depth, capacity, g, teache
     rt = runtime(dev)
     K, pyr_caps = capacity.gen[g]
     cnt2 = capacity.kept2(g)
-    n_cnt = info(coords_all).cnt
-    sel = torch.empty(max(n_all, 1), dtype=torch.int32, device=dev)
-    wsb = _lib.query('sgnn_compact_ws_bytes', n_all)
-    ws = rt.workspace(wsb)
     kept, kept8 = cnt2[0:1], cnt2[1:2]
     locs = _inherit_bounds(torch.empty(K, 4, dtype=torch.int32, device=dev), coords_all)
-    if FUSED_GLUE:       # the kept sites' coordinates are written by the compaction's own write kernel
-        if teacher is None:
-            _lib.call('sgnn_compact_sigmoid_cap_locs', ptr(logits), stride, n_all, ptr(n_cnt), ptr(coords_all), ptr(sel),
-                      ptr(locs), ptr(cnt2), K, ptr(rt.status32), ptr(ws), wsb)
-        else:
-            B, _, d0, d1, d2 = (int(v) for v in teacher.shape)
-            _lib.call('sgnn_compact_dense_cap_locs', ptr(coords_all), n_all, ptr(n_cnt), ptr(teacher), B, d0, d1, d2,
-                      ptr(sel), ptr(locs), ptr(cnt2), K, ptr(rt.status32), ptr(ws), wsb)
-    else:
-        if teacher is None:
-            _lib.call('sgnn_compact_sigmoid_cap', ptr(logits), stride, n_all, ptr(n_cnt), ptr(sel), ptr(cnt2), K,
-                      ptr(rt.status32), ptr(ws), wsb)
-        else:
-            B, _, d0, d1, d2 = (int(v) for v in teacher.shape)
-            _lib.call('sgnn_compact_dense_cap', ptr(coords_all), n_all, ptr(n_cnt), ptr(teacher), B, d0, d1, d2, ptr(sel),
-                      ptr(cnt2), K, ptr(rt.status32), ptr(ws), wsb)
+    # FUSED_GLUE: the kept sites' coordinates are written by the compaction's own write kernel
+    sel = _compact(rt, n_all, max(n_all, 1), logits, stride, coords_all, teacher, cap=(info(coords_all).cnt, cnt2, K),
+                   locs=locs if FUSED_GLUE else None)
+    if not FUSED_GLUE:
         _lib.call('sgnn_gather_rows_dn', ptr(coords_all), 4, ptr(sel), ptr(kept), K, ptr(locs))
     attach(locs, cnt=kept, cnt8=kept8)
     if depth >= 1:
@@ -638,10 +631,7 @@ def compact_capped(logits, stride, n_all, coords_all, depth, capacity, g, teache
 
 def compact_mask(mask_u8, n):
     rt = runtime(mask_u8.device)
-    sel = torch.empty(max(n, 1), dtype=torch.int32, device=mask_u8.device)
-    wsb = _lib.query('sgnn_compact_ws_bytes', n)
-    ws = rt.workspace(wsb)
-    _lib.call('sgnn_compact_mask', ptr(mask_u8), n, ptr(sel), ptr(rt.state), ptr(ws), wsb)
+    sel = _compact(rt, n, max(n, 1), mask=mask_u8)
     count = rt.read_count()
     return sel[:count], count
 
@@ -657,9 +647,7 @@ def _inherit_bounds(coords, parent, scale=1):
 
 def gather_coords(coords32, sel, m):
     """coords rows are 16-byte rows: reuse the fp32 row gather as a pure bit copy."""
-    out = torch.empty(m, 4, dtype=torch.int32, device=coords32.device)
-    _lib.call('sgnn_gather_rows', ptr(coords32), 4, ptr(sel), m, ptr(out))
-    return _inherit_bounds(out, coords32)
+    return _inherit_bounds(gather_rows_raw(coords32, 4, sel, m, torch.int32), coords32)
 
 
 def expand8_coords(coords32, with_i64=False):
@@ -691,8 +679,4 @@ def coords_to_i64(coords32):
     made = info(coords32).i64       # expand8_coords(with_i64=True) already wrote them
     if made is not None:
         return made
-    n = coords32.shape[0]
-    out = torch.empty(n, 4, dtype=torch.int64, device=coords32.device)
-    cnt = info(coords32).cnt
-    _lib.call('sgnn_coords_to_i64', ptr(coords32), n, ptr(out), ptr(cnt))
-    return out if cnt is None else attach(out, cnt=cnt)
+    return rows_i64(coords32, coords32.shape[0], info(coords32).cnt)

@@ -56,11 +56,14 @@ class _Runtime(object):
         It IS the weight-gradient lane's stream (idle during the forward pass): a third concurrently active stream was
         measured to collide with the training stream on one hardware pipe on some runs — both queues then stall
         40-70 us at every switch (18.8 instead of 6.2 ms per step, profiles/r03t_trace_summary.txt)."""
+        return self._side()
+
+    def _side(self):
+        """The one side stream, created (without a workspace yet) on first use."""
         if getattr(self, '_side_stream', None) is None:
             self._side_stream = torch.cuda.Stream(device=self.device, priority=SIDE_PRIORITY)
             self._side_ws = None
-        self._pyr_stream = self._side_stream
-        return self._pyr_stream
+        return self._side_stream
 
     def side_lane(self, nbytes):
         """Second stream + private workspace for the weight-gradient lane of sgnn_prog_backward (registered with the
@@ -70,9 +73,7 @@ class _Runtime(object):
                 _lib.query('sgnn_prog_set_side_stream', None, None, 0)
                 self._side_on = False
             return
-        if getattr(self, '_side_stream', None) is None:
-            self._side_stream = torch.cuda.Stream(device=self.device, priority=SIDE_PRIORITY)
-            self._side_ws = None
+        self._side()
         if self._side_ws is None or self._side_ws.numel() < nbytes or not getattr(self, '_side_on', False):
             if self._side_ws is None or self._side_ws.numel() < nbytes:
                 if self._side_ws is not None:
@@ -252,9 +253,15 @@ class Grid(object):
         return self._nbr
 
     def locations_i64(self):
-        out = torch.empty(self.n, 4, dtype=torch.int64, device=self.device)
-        _lib.call('sgnn_coords_to_i64', ptr(self.coords), self.n, ptr(out), ptr(self.cnt))
-        return out if self.cnt is None else attach(out, cnt=self.cnt)
+        return rows_i64(self.coords, self.n, self.cnt)
+
+
+def rows_i64(coords32, n, cnt):
+    """The reference's LongTensor rows of n int32 sites; cnt (capacity mode: their live count, device int64[1]) travels
+    with the result."""
+    out = torch.empty(n, 4, dtype=torch.int64, device=coords32.device)
+    _lib.call('sgnn_coords_to_i64', ptr(coords32), n, ptr(out), ptr(cnt))
+    return out if cnt is None else attach(out, cnt=cnt)
 
 
 class Down2(object):

@@ -9,6 +9,9 @@ Which set-up reaches which kernel:
       test_compact_mask_beyond_inline_limit (n = 4096 x 2048 + 1, default switches) takes the automatic fall-back to
       the three-launch form above SCAN_INLINE_MAX blocks.
   sgnn_coords_from_i64 / _to_i64, sgnn_expand8_coords / _i64, sgnn_dense_coords, sgnn_hash_build / _lookup: one kernel each.
+  The test_wrapper* cases at the end go through sgnn_amd.scn.functions instead of the library: compact_sigmoid, compact_mask,
+      compact_sigmoid_plan and compact_capped on 300 candidates of a batch-2 8x8x8 volume against a NumPy selection, each
+      asserting which of the seven entry points its switches (teacher volume, capacity, FUSED_GLUE, metadata.CHAIN) chose.
 
 Sizes sit on the 256-thread and 2048-item edges; masks are none / all / alternating / first / last / random / one whole
 2048 block empty.  Outputs lie in sentinel buffers: sel past the total, locs past min(total, keep_cap) and rows past a
@@ -356,3 +359,93 @@ def test_hash_build_lookup(cloud):
     assert st == R.STATUS_COORD_RANGE | R.STATUS_DUPLICATE
     # either of the two rows of the repeated site may win; every other query answers as before
     assert set(np.nonzero(got != want)[0]) <= set(np.nonzero((q == sites[3]).all(1))[0])
+
+
+# ---- the host wrappers of sgnn_amd.scn.functions: each of the seven entry points through the wrapper that chooses it ----
+
+W_N, W_DIMS, W_BATCH, W_CAP = 300, (8, 8, 8), 2, 512
+
+
+@pytest.fixture(scope='module')
+def wrapper_case():
+    """300 distinct candidate sites of a batch-2 8x8x8 volume in random order, with stride-2 logits and a teacher volume
+    that keep two different subsets of them; everything the NumPy selections below need."""
+    vol = int(np.prod(W_DIMS))
+    cells = np.random.default_rng(300).permutation(vol * W_BATCH)[:W_N]
+    b, v = cells // vol, cells % vol
+    coords = np.stack([v // (W_DIMS[1] * W_DIMS[2]), (v // W_DIMS[2]) % W_DIMS[1], v % W_DIMS[2], b], 1).astype(np.int32)
+    by_logit = R.masks(W_N)['random']
+    teacher = np.where(np.random.default_rng(8).random((W_BATCH,) + W_DIMS) < 0.4, 1.0, 0.5).astype(np.float32)
+    by_teacher = R.dense_predicate(coords, teacher)
+    assert 0 < by_logit.sum() < W_CAP and 0 < by_teacher.sum() < W_CAP and (by_logit != by_teacher).any()
+    assert by_logit[256:].any() and by_teacher[256:].any()
+    return dict(coords=coords, dev_coords=torch.from_numpy(coords).cuda(), logits=torch.from_numpy(_logits(by_logit)).cuda(),
+                teacher=torch.from_numpy(teacher[:, None].copy()).cuda(), keep={False: by_logit, True: by_teacher})
+
+
+@pytest.fixture
+def compact_names(monkeypatch):
+    """The sgnn_compact_* entry points called while the test runs; the calls go through unchanged."""
+    log, real = [], L().call
+
+    def spy(name, *args):
+        if name.startswith('sgnn_compact'):
+            log.append(name)
+        return real(name, *args)
+    monkeypatch.setattr(L(), 'call', spy)
+    return log
+
+
+def test_wrappers_compact_sigmoid_and_compact_mask(wrapper_case, compact_names):
+    from sgnn_amd.scn import functions as F_
+    c = wrapper_case
+    want = np.nonzero(c['keep'][False])[0].astype(np.int32)
+    sel, count = F_.compact_sigmoid(c['logits'], 2, W_N)
+    assert count == len(want)
+    R.assert_same_bits(sel.cpu().numpy(), want, 'compact_sigmoid')
+    sel, count = F_.compact_mask(torch.from_numpy(c['keep'][False].astype(np.uint8)).cuda(), W_N)
+    assert count == len(want)
+    R.assert_same_bits(sel.cpu().numpy(), want, 'compact_mask')
+    assert compact_names == ['sgnn_compact_sigmoid', 'sgnn_compact_mask']
+
+
+@pytest.mark.parametrize('teacher', [False, True], ids=['logits', 'teacher'])
+@pytest.mark.parametrize('chain', [True, False], ids=['chain', 'one_level'])
+def test_wrapper_compact_sigmoid_plan(wrapper_case, compact_names, monkeypatch, chain, teacher):
+    from sgnn_amd.scn import functions as F_, metadata as MD
+    from sgnn_amd.scn.sites import info
+    monkeypatch.setattr(MD, 'CHAIN', chain)
+    c = wrapper_case
+    want = np.nonzero(c['keep'][teacher])[0].astype(np.int32)
+    what = 'compact_sigmoid_plan chain=%s teacher=%s' % (chain, teacher)
+    sel, count, locs = F_.compact_sigmoid_plan(c['logits'], 2, W_N, c['dev_coords'], 1, c['teacher'] if teacher else None)
+    assert count == len(want), what
+    R.assert_same_bits(sel.cpu().numpy(), want, what + ' sel')
+    R.assert_same_bits(locs.cpu().numpy(), c['coords'][want], what + ' locs')
+    assert (info(locs).plan is not None) == chain, what
+    assert compact_names == ['sgnn_compact_dense' if teacher else 'sgnn_compact_sigmoid'], what
+
+
+@pytest.mark.parametrize('teacher', [False, True], ids=['logits', 'teacher'])
+@pytest.mark.parametrize('fused', [True, False], ids=['locs', 'gather'])
+def test_wrapper_compact_capped(wrapper_case, compact_names, monkeypatch, fused, teacher):
+    """Capacity 512 >= the kept count: no overflow status; the counts stay on the device until the test reads them."""
+    from sgnn_amd.scn import functions as F_, metadata as MD
+    from sgnn_amd.scn.capacity import Capacity
+    from sgnn_amd.scn.sites import info
+    monkeypatch.setattr(F_, 'FUSED_GLUE', fused)
+    c = wrapper_case
+    want = np.nonzero(c['keep'][teacher])[0].astype(np.int32)
+    what = 'compact_capped fused=%s teacher=%s' % (fused, teacher)
+    cap = Capacity('cuda', 1024, [], [(W_CAP, [W_CAP, W_CAP])])
+    rt = MD.runtime(torch.device('cuda', torch.cuda.current_device()))
+    syncs = rt.syncs
+    sel, K, locs = F_.compact_capped(c['logits'], 2, W_N, c['dev_coords'], 0, cap, 0, c['teacher'] if teacher else None)
+    assert rt.syncs == syncs, what + ': capacity mode must not read anything back'
+    assert K == W_CAP and tuple(sel.shape) == (W_N,) and tuple(locs.shape) == (W_CAP, 4) and locs.dtype == torch.int32
+    assert cap.kept2(0).cpu().tolist() == [len(want), 8 * len(want)], what
+    assert info(locs).cnt.data_ptr() == cap.kept2(0).data_ptr() and int(info(locs).cnt8.item()) == 8 * len(want)
+    R.assert_same_bits(sel.cpu().numpy()[:len(want)], want, what + ' sel')
+    R.assert_same_bits(locs.cpu().numpy()[:len(want)], c['coords'][want], what + ' locs')
+    rt.check_status()
+    assert compact_names == ['sgnn_compact_%s_cap%s' % ('dense' if teacher else 'sigmoid', '_locs' if fused else '')], what

@@ -907,6 +907,34 @@ int sgnn_track_system(const float *depth, const float *live_normal, int h, int w
                       int64_t ws_bytes, sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Point sets registered against a volume (sgnn_amd.register; rules in INTEGRATION.md section R): point-to-SDF
+ * Gauss-Newton.  The residual of a source point is the trilinear sample of the destination's sdf at its transformed
+ * position, its Jacobian the gradient of the same interpolant; the system has the layout of sgnn_track_system, and
+ * the 6x6 solve and the update of the transform stay on the host.
+ * ------------------------------------------------------------------------- */
+/* one transform of sgnn_register_system (96 bytes; the record table is a device array of these) */
+typedef struct sgnn_register_pair {
+  float t[12]; /* rows 0..2 of T: source world (x,y,z,1) -> destination world, fp32; NaN = non-finite record, empty
+                  system */
+  float w[12]; /* rows 0..2 of the destination's world2grid: world (x,y,z,1) -> voxel coordinates, fp32 */
+} sgnn_register_pair;
+#define SGNN_REGISTER_MAX_BLOCKS 256 /* partial sums per record that sgnn_register_system keeps in its workspace */
+/* out (npairs, 32) f64: per record the 21 sums of the upper triangle of J^T J (row-major), the 6 of J^T r, the sum of
+ * r^2, the number of associated points, and three zeros (rules 2-7).  points (npoints, 3) f32 in the source world; sdf
+ * (dz, dy, dx) f32 of the destination in any unit, band and max_dist in the same unit; min_grad2: the smallest squared
+ * length of the world-space gradient an association may have, rounded by the caller.  Every record runs against the
+ * same points and the same volume.  residual (npairs, npoints) f32 (NaN = no association) and cell (npairs, npoints)
+ * i32 ((fz * dy + fy) * dx + fx of the sample's cell, or -1) may be NULL.  ws: at least npairs *
+ * min(ceil(npoints / 256), SGNN_REGISTER_MAX_BLOCKS) * 256 bytes; the number of partial sums depends on npoints alone
+ * and they are added in index order, so neither npairs nor the launch shows in any bit of the result.
+ * npoints < 2^31 - 65536; npairs <= 65535; dx, dy, dz >= 2 and dx * dy * dz < 2^31; band, max_dist > 0;
+ * min_grad2 >= 0.  npoints == 0 or npairs == 0 launches nothing and writes nothing. */
+int sgnn_register_system(const float *points, int npoints, const float *sdf, int dx, int dy, int dz,
+                         const sgnn_register_pair *pairs, int npairs, float band, float max_dist, float min_grad2,
+                         double *out, float *residual, int32_t *cell, void *ws, int64_t ws_bytes,
+                         sgnn_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Connected components of volumes and meshes (sgnn_amd.components; rules in INTEGRATION.md section J): lock-free
  * union-find on parent[] (i32, one slot per voxel or vertex; -1 = background / unreferenced).  Larger indices are
  * hooked onto smaller ones, so parent[i] <= i at all times and the root of a finished component is its smallest index.

@@ -9,6 +9,7 @@ Package contents (only what the hot path of SURVEY.md §8 needs):
   train.py     one training step + data-parallel gradient all-reduce (torch/train.py:245-268)
   synth.py     synthetic TSDF blocks in the layout scene_dataloader.collate emits
   track.py     depth frames tracked against a TSDF volume: poses for fusion
+  register.py  point sets and volumes registered against a TSDF volume: transforms for regrid.merge (section R)
 """
 __version__ = '0.1.0'
 
@@ -19,7 +20,7 @@ def __getattr__(name):
     if name == 'bf16_inference':
         from .scn.program import bf16_inference
         return bf16_inference
-    if name == 'track':             # sgnn_amd.track without an import statement of its own, as lazily as the above
+    if name in ('track', 'register'):   # sgnn_amd.track / .register without an import statement of their own, as lazily as the above
         import importlib
-        return importlib.import_module('.track', __name__)
+        return importlib.import_module('.' + name, __name__)
     raise AttributeError(name)

@@ -935,6 +935,46 @@ int sgnn_register_system(const float *points, int npoints, const float *sdf, int
                          sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * The gravity-aligned room frame of a volume (sgnn_amd.upright; rules in INTEGRATION.md section S): votes of the
+ * surface normals of a TSDF volume.  A surface voxel is an interior voxel whose sdf and six axis neighbours are finite
+ * with |.| < band and whose own |sdf| < surface; its normal is the central difference taken to the world through the
+ * transpose of world2grid's 3x3 (rule S.1).  The three entry points walk the same voxels: sdf (dz, dy, dx) f32 on the
+ * device, dx * dy * dz < 2^31, band and surface > 0 in the sdf's unit; world2grid (and grid2world, its inverse as the
+ * caller rounded it): 12 finite floats on the host, rows 0..2.  Every output is an integer count or a 2^20 fixed-point
+ * integer sum that the call adds into (the caller zeroes it), so neither the launch nor the order of the atomics
+ * shows in any bit.  A volume with a dimension below 3 has no interior voxel: nothing is launched or written.  The
+ * peak search, the cone iteration, the yaw and the floor level stay on the host.
+ * ------------------------------------------------------------------------- */
+/* one candidate axis of sgnn_upright_sums (48 bytes; the record table is a device array of these); a non-finite entry
+ * makes the record empty */
+typedef struct sgnn_upright_axis {
+  float u[3];     /* the axis, unit length */
+  float e1[3];    /* two unit vectors that span the plane normal to u: the frame the wall angle is measured in */
+  float e2[3];
+  float cos_cone; /* a normal n votes for the axis when |n . u| >= cos_cone */
+  float sin_wall; /* a normal n is a wall normal when |n . u| <= sin_wall */
+  float pad[1];
+} sgnn_upright_axis;
+#define SGNN_UPRIGHT_MAX_HEIGHT_BINS 4096 /* the most bins per row of sgnn_upright_heights */
+/* hist (6, bins, bins) i32: the cube-map histogram of the unnormalised normals (rule S.2), bin (f * bins + iv) * bins +
+ * iu with f = 2 * major axis + (negative).  bins is 8, 16 or 32. */
+int sgnn_upright_histogram(const float *sdf, int dx, int dy, int dz, const float *world2grid, float band, float surface,
+                           int bins, int32_t *hist, sgnn_stream_t stream);
+/* out (nrecords, 8) i64 (rule S.4): per record the 2^20 fixed-point sums of sign(n . u) n over the normals inside the
+ * cone (x, y, z), the number of those with n . u > 0 and with n . u < 0, the 2^20 fixed-point sums of cos 4a and sin 4a
+ * of the wall normals' angle a in the (e1, e2) frame, and the number of wall normals.  records: device array; every
+ * record runs against the same volume in one launch.  nrecords <= 65535; 0 launches nothing. */
+int sgnn_upright_sums(const float *sdf, int dx, int dy, int dz, const float *world2grid, float band, float surface,
+                      const sgnn_upright_axis *records, int nrecords, int64_t *out, sgnn_stream_t stream);
+/* hist (2, nbins) i32 (rule S.5): heights h = (p - v n) . up of the surface voxels carried to the zero crossing along
+ * their normals, bin floor((h - h0) / bin), voxels outside [0, nbins) dropped; row 0 the normals with n . up >=
+ * cos_cone (floors), row 1 those with n . up <= -cos_cone (ceilings).  up: 3 finite floats on the host.  cos_cone > 0, bin > 0;
+ * 1 <= nbins <= SGNN_UPRIGHT_MAX_HEIGHT_BINS. */
+int sgnn_upright_heights(const float *sdf, int dx, int dy, int dz, const float *world2grid, const float *grid2world,
+                         float band, float surface, const float *up, float cos_cone, float h0, float bin, int nbins,
+                         int32_t *hist, sgnn_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Connected components of volumes and meshes (sgnn_amd.components; rules in INTEGRATION.md section J): lock-free
  * union-find on parent[] (i32, one slot per voxel or vertex; -1 = background / unreferenced).  Larger indices are
  * hooked onto smaller ones, so parent[i] <= i at all times and the root of a finished component is its smallest index.

@@ -28,10 +28,34 @@ def host(x, dtype):
     return np.ascontiguousarray(np.asarray(x, dtype=dtype))
 
 
+def source_device(*inputs):
+    """The device the inputs name: that of the first device tensor among them, the current one if there is none."""
+    for x in inputs:
+        if torch.is_tensor(x) and x.is_cuda:
+            return device(x.device)
+    return device()
+
+
+def positive(name, v):
+    """v as fp32, which must be positive and finite."""
+    v = np.float32(v)
+    if not (v > 0 and np.isfinite(v)):
+        raise ValueError('%s must be positive' % name)
+    return v
+
+
+def invertible(m, name, dtype=np.float64):
+    """m as a host (4, 4) matrix of dtype, which must be finite with a determinant (fp64) that is not 0."""
+    m = host(m, dtype)
+    if m.shape != (4, 4) or not np.isfinite(m).all() or abs(np.linalg.det(m.astype(np.float64))) == 0:
+        raise ValueError('%s must be an invertible (4, 4) matrix' % name)
+    return m
+
+
 def mesh_shape(verts, faces, *more):
     """First half of a mesh hand-over: the device the inputs (and `more`, which may be None) name, and (nv, nt) once
     verts and faces are (N, 3).  The caller's own limits come between this and mesh_upload."""
-    dev = device(next((x.device for x in (verts, faces) + more if torch.is_tensor(x) and x.is_cuda), None))
+    dev = source_device(verts, faces, *more)
     for name, x in (('verts', verts), ('faces', faces)):
         shape = tuple(x.shape)
         if len(shape) != 2 or shape[1] != 3:

@@ -1,6 +1,7 @@
 // The 32-double Gauss-Newton system of INTEGRATION.md section I rule 6 (and section R rule 7): what a lane adds for one
-// association, how a block folds its lanes into one partial, and the kernel that adds the partials.  register.hip
-// includes this; track.hip still carries its own copy of the same three pieces.
+// association, how a block folds its lanes into one partial, the kernel that adds the partials, and the host tail
+// that sizes the grid and launches that kernel.  track.hip and register.hip build their systems from this and differ
+// in the residual alone.
 //
 // Every term is the product of two fp32 values and therefore exact in fp64; only the order of the additions is ours,
 // and it is fixed: a lane's own terms in the order it meets them, an xor butterfly inside the wave, the four waves of a
@@ -58,4 +59,20 @@ static __global__ __launch_bounds__(64) void k_gn_finish(const double *__restric
   double s = p[0];
   for (int b = 1; b < nblk; ++b) s += p[(int64_t)b * GN_ENTRIES];
   out[(int64_t)blockIdx.x * GN_ENTRIES + t] = s;
+}
+
+// What the sgnn_*_system entry points share once their own arguments are checked: nblk = min(ceil(n / GN_BLOCK),
+// max_blocks), a function of n alone; the workspace check; `system(nblk)`, the caller's launch of its system kernel on
+// a (nblk, npairs) grid; k_gn_finish.
+template <class SystemLaunch>
+static inline int gn_launch(int64_t n, int max_blocks, int npairs, void *ws, int64_t ws_bytes, double *out,
+                            hipStream_t s, SystemLaunch system) {
+  const int64_t want = (n + GN_BLOCK - 1) / GN_BLOCK;
+  const int nblk = (int)(want < max_blocks ? want : max_blocks);
+  SGNN_CHECK_ARG(ws_bytes >= (int64_t)npairs * nblk * GN_ENTRIES * (int64_t)sizeof(double));
+  system(nblk);
+  SGNN_CHECK_LAUNCH();
+  SGNN_LAUNCH(k_gn_finish, dim3(npairs), dim3(64), 0, s, (const double *)ws, nblk, out);
+  SGNN_CHECK_LAUNCH();
+  return SGNN_OK;
 }

@@ -22,8 +22,6 @@ namespace {
 
 constexpr int BLOCK = GN_BLOCK;
 
-__device__ __forceinline__ bool finite_f(float v) { return fabsf(v) < INFINITY; }   // false for a NaN
-
 __device__ __forceinline__ float lerp(float p, float q, float a) { return p + a * (q - p); }
 
 __global__ __launch_bounds__(BLOCK) void k_register_system(const float *__restrict__ points, int npts,
@@ -102,14 +100,9 @@ SGNN_EXPORT int sgnn_register_system(const float *points, int npoints, const flo
   SGNN_CHECK_ARG(band > 0.f && max_dist > 0.f && min_grad2 >= 0.f);                                  // a NaN fails
   if (npoints == 0 || npairs == 0) return SGNN_OK;
   SGNN_CHECK_ARG(points && sdf && pairs && out && ws);
-  const int64_t want = ((int64_t)npoints + BLOCK - 1) / BLOCK;
-  const int nblk = (int)(want < SGNN_REGISTER_MAX_BLOCKS ? want : SGNN_REGISTER_MAX_BLOCKS);   // a function of npoints alone
-  SGNN_CHECK_ARG(ws_bytes >= (int64_t)npairs * nblk * GN_ENTRIES * (int64_t)sizeof(double));
   hipStream_t s = (hipStream_t)stream;
-  SGNN_LAUNCH(k_register_system, dim3(nblk, npairs), dim3(BLOCK), 0, s, points, npoints, sdf, dx, dy, dz, pairs, band,
-              max_dist, min_grad2, (double *)ws, residual, cell);
-  SGNN_CHECK_LAUNCH();
-  SGNN_LAUNCH(k_gn_finish, dim3(npairs), dim3(64), 0, s, (const double *)ws, nblk, out);
-  SGNN_CHECK_LAUNCH();
-  return SGNN_OK;
+  return gn_launch(npoints, SGNN_REGISTER_MAX_BLOCKS, npairs, ws, ws_bytes, out, s, [&](int nblk) {
+    SGNN_LAUNCH(k_register_system, dim3(nblk, npairs), dim3(BLOCK), 0, s, points, npoints, sdf, dx, dy, dz, pairs, band,
+                max_dist, min_grad2, (double *)ws, residual, cell);
+  });
 }

@@ -9,22 +9,20 @@
 //                    keeps the 28 sums of rule 6 as fp64 accumulators and its pixel count; the pair record is
 //                    wave-uniform and arrives by scalar loads.  Neighbouring live pixels associate to neighbouring
 //                    model pixels, so the model gathers are nearly coalesced; no LDS staging.  A lane without an
-//                    association adds zeros.  Reduction: a fixed xor butterfly inside the wave, the four waves of a
-//                    block through LDS in wave order, one 32-double partial per block to the workspace.
-//   k_track_finish   one block per pair adds the partials in index order.
+//                    association adds zeros.  Reduction: csrc/gn_system.h, one 32-double partial per block.
+//   k_gn_finish      one block per pair adds the partials in index order (csrc/gn_system.h).
 //
-// Every term of rule 6 is the product of two fp32 values, exact in fp64; only the order of the additions is ours,
-// and it is a function of (h, w) alone: no floating-point atomics, the same bits on every call.
+// The order of the additions is a function of (h, w) alone: no floating-point atomics, the same bits on every call.
 //
 // Built with -ffp-contract=off (Makefile): every product and sum is rounded on its own.
 #include <math.h>
 #include "common.h"
+#include "gn_system.h"
+#include "tsdf.h"
 
 namespace {
 
-constexpr int BLOCK = 256;
-
-__device__ __forceinline__ bool finite_f(float v) { return fabsf(v) < INFINITY; }   // false for a NaN
+constexpr int BLOCK = GN_BLOCK;
 
 // rule 9
 __global__ __launch_bounds__(BLOCK) void k_track_halve(const float *__restrict__ in, int total, int h, int w, int h2,
@@ -84,14 +82,6 @@ __global__ __launch_bounds__(BLOCK) void k_track_normals(const float *__restrict
   normal[(int64_t)idx * 3 + 2] = nz;
 }
 
-__device__ __forceinline__ double wave_allsum(double v) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);             // every lane ends with the same bits
-  return v;
-}
-
-constexpr int NSUM = 28;   // 21 of J^T J, 6 of J^T r, r^2
-
 template <bool ANGLE>
 __global__ __launch_bounds__(BLOCK) void k_track_system(const float *__restrict__ depth,
                                                        const float *__restrict__ live_normal, int h, int w,
@@ -100,7 +90,7 @@ __global__ __launch_bounds__(BLOCK) void k_track_system(const float *__restrict_
                                                        const sgnn_track_pair *__restrict__ pairs, float max_dist2,
                                                        float cos_min, double *__restrict__ ws,
                                                        float *__restrict__ residual, int32_t *__restrict__ assoc) {
-  __shared__ double part[4][32];
+  __shared__ double part[4][GN_ENTRIES];
   const int pair = (int)blockIdx.y;
   const sgnn_track_pair &P = pairs[pair];
   const float *T = P.t;
@@ -111,9 +101,9 @@ __global__ __launch_bounds__(BLOCK) void k_track_system(const float *__restrict_
   const int64_t live0 = (int64_t)pair * npix;
   const float *md = model_depth + (int64_t)pair * hm * wm;
   const float *mn = model_normal + (int64_t)pair * hm * wm * 3;
-  double acc[NSUM];
+  double acc[GN_NSUM];
 #pragma unroll
-  for (int k = 0; k < NSUM; ++k) acc[k] = 0.0;
+  for (int k = 0; k < GN_NSUM; ++k) acc[k] = 0.0;
   int count = 0;
   for (int px = (int)blockIdx.x * BLOCK + (int)threadIdx.x; px < npix; px += (int)gridDim.x * BLOCK) {
     const int j = px / w, i = px - j * w;
@@ -121,9 +111,9 @@ __global__ __launch_bounds__(BLOCK) void k_track_system(const float *__restrict_
     const float d = depth[live0 + px];
     bool ok = pose_ok && finite_f(d) && d > 0.f;
     const float lx = __fdiv_rn((float)i - cxl, fxl) * d, ly = __fdiv_rn((float)j - cyl, fyl) * d;
-    const float qx = ((T[0] * lx + T[1] * ly) + T[2] * d) + T[3];
-    const float qy = ((T[4] * lx + T[5] * ly) + T[6] * d) + T[7];
-    const float qz = ((T[8] * lx + T[9] * ly) + T[10] * d) + T[11];
+    float q[3];
+    tsdf_affine(T, lx, ly, d, q);
+    const float qx = q[0], qy = q[1], qz = q[2];
     // rule 3
     ok = ok && qz > 0.f;
     const float u = roundf(__fdiv_rn(qx * fxm, qz) + cxm), v = roundf(__fdiv_rn(qy * fym, qz) + cym);
@@ -156,41 +146,10 @@ __global__ __launch_bounds__(BLOCK) void k_track_system(const float *__restrict_
     J[4] = ok ? ny : 0.f;
     J[5] = ok ? nz : 0.f;
     J[6] = ok ? r : 0.f;
-    // rule 6: exact products, fp64 sums
-    int k = 0;
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-      for (int b = a; b < 6; ++b) acc[k++] += (double)J[a] * (double)J[b];
-#pragma unroll
-    for (int a = 0; a < 7; ++a) acc[21 + a] += (double)J[a] * (double)J[6];
+    gn_accumulate(acc, J);                          // rule 6: exact products, fp64 sums
     count += ok ? 1 : 0;
   }
-  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
-#pragma unroll
-  for (int k = 0; k < NSUM; ++k) acc[k] = wave_allsum(acc[k]);
-  const double n = wave_allsum((double)count);                          // integers: exact
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < NSUM; ++k) part[wave][k] = acc[k];
-    part[wave][28] = n;
-    part[wave][29] = part[wave][30] = part[wave][31] = 0.0;
-  }
-  __syncthreads();
-  if (threadIdx.x < 32) {
-    const int t = (int)threadIdx.x;
-    ws[((int64_t)pair * gridDim.x + blockIdx.x) * 32 + t] = ((part[0][t] + part[1][t]) + part[2][t]) + part[3][t];
-  }
-}
-
-// the partials of one pair in index order; thread t owns entry t of the 32
-__global__ __launch_bounds__(64) void k_track_finish(const double *__restrict__ ws, int nblk, double *__restrict__ out) {
-  const int t = (int)threadIdx.x;
-  if (t >= 32) return;
-  const double *p = ws + (int64_t)blockIdx.x * nblk * 32 + t;
-  double s = p[0];
-  for (int b = 1; b < nblk; ++b) s += p[(int64_t)b * 32];
-  out[(int64_t)blockIdx.x * 32 + t] = s;
+  gn_block_reduce(acc, count, part, ws + ((int64_t)pair * gridDim.x + blockIdx.x) * GN_ENTRIES);
 }
 
 }  // namespace
@@ -232,19 +191,14 @@ SGNN_EXPORT int sgnn_track_system(const float *depth, const float *live_normal, 
   SGNN_CHECK_ARG(max_dist2 > 0.f);
   if (npairs == 0) return SGNN_OK;
   SGNN_CHECK_ARG(depth && model_depth && model_normal && pairs && out && ws);
-  const int64_t want = ((int64_t)h * w + BLOCK - 1) / BLOCK;
-  const int nblk = (int)(want < SGNN_TRACK_MAX_BLOCKS ? want : SGNN_TRACK_MAX_BLOCKS);   // a function of (h, w) alone
-  SGNN_CHECK_ARG(ws_bytes >= (int64_t)npairs * nblk * 32 * (int64_t)sizeof(double));
   hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(nblk, npairs);
-  if (live_normal)
-    SGNN_LAUNCH((k_track_system<true>), grid, dim3(BLOCK), 0, s, depth, live_normal, h, w, model_depth, model_normal, hm,
-                wm, pairs, max_dist2, cos_min, (double *)ws, residual, assoc);
-  else
-    SGNN_LAUNCH((k_track_system<false>), grid, dim3(BLOCK), 0, s, depth, live_normal, h, w, model_depth, model_normal,
-                hm, wm, pairs, max_dist2, cos_min, (double *)ws, residual, assoc);
-  SGNN_CHECK_LAUNCH();
-  SGNN_LAUNCH(k_track_finish, dim3(npairs), dim3(64), 0, s, (const double *)ws, nblk, out);
-  SGNN_CHECK_LAUNCH();
-  return SGNN_OK;
+  return gn_launch((int64_t)h * w, SGNN_TRACK_MAX_BLOCKS, npairs, ws, ws_bytes, out, s, [&](int nblk) {
+    const dim3 grid(nblk, npairs);
+    if (live_normal)
+      SGNN_LAUNCH((k_track_system<true>), grid, dim3(BLOCK), 0, s, depth, live_normal, h, w, model_depth, model_normal,
+                  hm, wm, pairs, max_dist2, cos_min, (double *)ws, residual, assoc);
+    else
+      SGNN_LAUNCH((k_track_system<false>), grid, dim3(BLOCK), 0, s, depth, live_normal, h, w, model_depth, model_normal,
+                  hm, wm, pairs, max_dist2, cos_min, (double *)ws, residual, assoc);
+  });
 }

@@ -7,6 +7,8 @@
 #include <math.h>
 #include "common.h"
 
+__device__ __forceinline__ bool finite_f(float v) { return fabsf(v) < INFINITY; }   // false for a NaN
+
 // ---- affine maps: rows 0..2 of a 4x4, row-major --------------------------------------------------------------------
 struct TsdfAffine { float m[12]; };
 

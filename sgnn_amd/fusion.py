@@ -20,7 +20,8 @@ import numpy as np
 import torch
 
 from . import _lib, data
-from ._glue import cameras, compact, device as _device, host as _host, to_device as _to_device
+from ._glue import (cameras, compact, device as _device, host as _host, source_device as _source_device,
+                    to_device as _to_device)
 
 # struct sgnn_fuse_frame (include/sgnn_hip.h)
 FRAME_DTYPE = np.dtype([('m', '<f4', (12,)), ('intr', '<f4', (4,)), ('box', '<i4', (6,)), ('offset', '<i8')])
@@ -63,7 +64,7 @@ def adapt_intrinsics(intrinsics, raw_hw, out_hw):
 def raw_depth_to_metric(raw_u16, depth_shift, out_hw, min_depth=0.1, max_depth=12.0, intrinsics=None):
     """uint16 frames (h_raw, w_raw) or (F, h_raw, w_raw) -> (metric fp32 depth on the device, (F,) h, w, with -inf
     for no data; the adapted intrinsics (fx, fy, cx, cy) as fp32 numpy, or None when none were given)."""
-    dev = _device(raw_u16.device if torch.is_tensor(raw_u16) and raw_u16.is_cuda else None)
+    dev = _source_device(raw_u16)
     if torch.is_tensor(raw_u16) and raw_u16.is_cuda and raw_u16.dtype in (torch.int16, getattr(torch, 'uint16', None)):
         raw = raw_u16.contiguous()
     else:
@@ -85,7 +86,7 @@ def pack_color(rgb, out_hw=None):
     torch, host or device -> the (F, h, w, 4) uint8 device stack TSDFVolume.integrate(color=) takes, resampled to
     out_hw = (h, w) by raw_depth_to_metric's nearest-index rule (None: the frames' own size).  A = 255 where the pixel
     has a colour (every pixel of 3-channel input, a != 0 of 4-channel input), else 0."""
-    dev = _device(rgb.device if torch.is_tensor(rgb) and rgb.is_cuda else None)
+    dev = _source_device(rgb)
     raw = _to_device(rgb if torch.is_tensor(rgb) else _host(rgb, np.uint8), torch.uint8, dev)
     if raw.dim() == 3:
         raw = raw[None]
@@ -100,7 +101,7 @@ def pack_color(rgb, out_hw=None):
 
 def bilateral(depth, sigma_d=2.0, sigma_r=0.1):
     """Bilateral filter of (h, w) or (F, h, w) metric depth (CameraUtil.h:25-63); -inf stays -inf."""
-    dev = _device(depth.device if torch.is_tensor(depth) and depth.is_cuda else None)
+    dev = _source_device(depth)
     d = _to_device(depth, torch.float32, dev)
     d3 = d[None] if d.dim() == 2 else d
     out = torch.empty_like(d3)

@@ -18,14 +18,14 @@ A guess is required (None is the identity): there is no global search.  The devi
 6x6 solve and the update of the transform are track.solve_step and track.se3_exp, on the host in fp64.
 """
 import collections
-import math
 
 import numpy as np
 import torch
 
-from . import _lib, fusion
-from ._glue import device as _device, host as _host, to_device as _to_device
-from .track import _Timer, se3_exp, solve_step, unpack  # noqa: F401  (unpack: the layout of a system is track's)
+from . import _gn, _lib, fusion  # noqa: F401  (_lib: the tests count launches through it)
+from ._glue import (host as _host, invertible as _invertible, positive as _gate, source_device as _source_device,
+                    to_device as _to_device)
+from ._gn import se3_exp, solve_step, unpack  # noqa: F401  (the layout of a system is shared with track)
 
 # struct sgnn_register_pair (include/sgnn_hip.h)
 PAIR_DTYPE = np.dtype([('t', '<f4', (12,)), ('w', '<f4', (12,))])
@@ -39,17 +39,6 @@ RegisterResult = collections.namedtuple('RegisterResult', 'T ok pairs rmse histo
 RegisterResult.__doc__ = """What align() found for one guess: T (4, 4) fp64, source world -> destination world (the
 guess when ok is false), ok, pairs and rmse (the sdf's unit) of the last iteration, and history: the number of
 associated points of every iteration run."""
-
-
-def _source_device(x):
-    return _device(x.device if torch.is_tensor(x) and x.is_cuda else None)
-
-
-def _gate(name, v):
-    v = np.float32(v)
-    if not (v > 0 and np.isfinite(v)):
-        raise ValueError('%s must be positive' % name)
-    return v
 
 
 def _matrices(T, name):
@@ -74,15 +63,10 @@ def pair_table(world2grid, T):
     nb = t64.shape[0]
     table = np.zeros(nb, dtype=PAIR_DTYPE)
     with np.errstate(all='ignore'):
-        t = t64[:, :3, :].astype(np.float32)
         w = w64[:3, :].astype(np.float32)
-    bad = ~np.isfinite(t).all(axis=(1, 2)) | ~np.isfinite(t64).all(axis=(1, 2))
-    if not (np.isfinite(w).all() and np.isfinite(w64).all()):
-        bad[:] = True
-        w = np.zeros_like(w)
-    t[bad] = np.nan
-    table['t'] = t.reshape(nb, 12)
-    table['w'] = w.reshape(12)
+    w_ok = np.isfinite(w).all() and np.isfinite(w64).all()
+    table['t'] = _gn.record_rows(t64[:, :3, :].reshape(nb, 12), np.isfinite(t64[:, 3]).all(axis=1) & w_ok)
+    table['w'] = w.reshape(12) if w_ok else 0
     return table
 
 
@@ -106,20 +90,14 @@ def _system(pts, sdf, table, band, max_dist, min_grad2, residual, cell, dev):
     """The launch: device fp32 points and sdf, a host record table -> (B, 32) fp64 on the device."""
     npts, nb = int(pts.shape[0]), int(table.shape[0])
     dz, dy, dx = (int(v) for v in sdf.shape)
-    out = torch.zeros((nb, 32), dtype=torch.float64, device=dev)
-    if nb == 0 or npts == 0:
+    if nb == 0 or npts == 0:                                                # no launch: nothing writes the outputs
         if residual is not None:
             residual.fill_(float('nan'))
         if cell is not None:
             cell.fill_(-1)
-        return out
-    nblk = min((npts + 255) // 256, MAX_BLOCKS)
-    ws = torch.empty(nb * nblk * 32, dtype=torch.float64, device=dev)
-    dev_table = torch.from_numpy(table.view(np.uint8)).to(dev)
-    _lib.call('sgnn_register_system', pts.data_ptr(), npts, sdf.data_ptr(), dx, dy, dz, dev_table.data_ptr(), nb,
-              float(band), float(max_dist), float(min_grad2), out.data_ptr(), _lib.ptr(residual), _lib.ptr(cell),
-              ws.data_ptr(), ws.numel() * 8)
-    return out
+    head = (pts.data_ptr(), npts, sdf.data_ptr(), dx, dy, dz)
+    return _gn.launch('sgnn_register_system', head, table, (band, max_dist, min_grad2), npts, MAX_BLOCKS,
+                      (residual, cell), dev)
 
 
 def _gates(band, max_dist, min_grad):
@@ -151,10 +129,7 @@ def normal_equations(points, sdf, world2grid, T, band, max_dist=None, min_grad=0
     if nb > MAX_PAIRS:
         raise ValueError('more than %d transforms in one call' % MAX_PAIRS)
     table = pair_table(world2grid, t64)
-    for name, t, dtype in (('residual', residual, torch.float32), ('cell', cell, torch.int32)):
-        if t is not None and not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and
-                                  tuple(t.shape) == (nb, npts)):
-            raise ValueError('%s must be a contiguous device %s tensor of shape %s' % (name, dtype, (nb, npts)))
+    _gn.check_per_item((nb, npts), residual, cell, 'cell')
     pts = _to_device(points, torch.float32, dev)
     return _system(pts, _to_device(sdf, torch.float32, dev), table, band, max_dist, min_grad2, residual, cell, dev)
 
@@ -194,33 +169,21 @@ def align(points, vol, guess=None, iterations=30, max_dist=None, min_grad=0.5, m
     w64 = _host(world2grid, np.float64)
     if w64.shape != (4, 4):
         raise ValueError('world2grid must be (4, 4), got %s' % (w64.shape,))
-    dev = sdf.device if torch.is_tensor(sdf) and sdf.is_cuda else _source_device(points)
+    dev = _source_device(sdf, points)
     pts = _to_device(points, torch.float32, dev)
     field = _to_device(sdf, torch.float32, dev)
-    T = guess64.copy()
-    alive = np.ones(nb, bool)
-    pairs, rmse = np.zeros(nb, np.int64), np.full(nb, np.nan)
-    history = [[] for _ in range(nb)]
-    tick = _Timer(timers)
+    run = _gn.Steps(guess64, min_pairs)
+    tick = _gn.Timer(timers)
     for _ in range(int(iterations)):
-        if not alive.any():
+        if not any(run.alive):
             break
-        current = np.where(alive[:, None, None], T, np.nan)
+        current = np.where(np.array(run.alive)[:, None, None], run.T, np.nan)
         systems = _system(pts, field, pair_table(w64, current), band, max_dist, min_grad2, None, None,
                           dev).cpu().numpy()                                 # 256 bytes per guess
         tick('system')
-        for b in np.nonzero(alive)[0]:
-            xi, n, e = solve_step(systems[b], min_pairs)
-            history[b].append(n)
-            pairs[b] = n
-            if xi is None:
-                alive[b], rmse[b] = False, np.nan
-                T[b] = guess64[b]
-                continue
-            rmse[b] = math.sqrt(e / n)
-            T[b] = se3_exp(xi) @ T[b]
+        run.step(systems)
         tick('solve')
-    out = [RegisterResult(T[b].copy(), bool(alive[b]), int(pairs[b]), float(rmse[b]), tuple(history[b]))
+    out = [RegisterResult(run.T[b].copy(), run.alive[b], run.pairs[b], run.rmse[b], tuple(run.history[b]))
            for b in range(nb)]
     return out[0] if single else out
 
@@ -260,10 +223,7 @@ def surface_points(vol_or_sdf, world2grid=None, band=None, stride=1):
     band = np.float32(np.inf) if band is None else np.float32(band)
     if not band > 0:
         raise ValueError('band must be positive')
-    w64 = _host(world2grid, np.float32).astype(np.float64)
-    if w64.shape != (4, 4) or not np.isfinite(w64).all() or abs(np.linalg.det(w64)) == 0:
-        raise ValueError('world2grid must be an invertible (4, 4) matrix')
-    m = np.linalg.inv(w64).astype(np.float32)
+    m = np.linalg.inv(_invertible(world2grid, 'world2grid', np.float32).astype(np.float64)).astype(np.float32)
     dev = _source_device(sdf)
     s = _to_device(sdf, torch.float32, dev)
     usable = torch.isfinite(s) & (s.abs() < float(band))
@@ -299,9 +259,7 @@ def apply(vol, T):
     """vol.copy() moved by T (4, 4), source world -> destination world: its world2grid becomes
     vol.world2grid . inv(T), formed in fp64 and rounded to fp32, so regrid.merge(room, apply(other, res.T)) is the
     registered merge."""
-    t = _host(T, np.float64)
-    if t.shape != (4, 4) or not np.isfinite(t).all() or abs(np.linalg.det(t)) == 0:
-        raise ValueError('T must be an invertible (4, 4) matrix')
+    t = _invertible(T, 'T')
     moved = vol.copy()
     moved.world2grid = (vol.world2grid.astype(np.float64) @ np.linalg.inv(t)).astype(np.float32)
     return moved

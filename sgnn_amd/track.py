@@ -21,8 +21,9 @@ import math
 import numpy as np
 import torch
 
-from . import _lib, raycast
-from ._glue import device as _device, host as _host, to_device as _to_device
+from . import _gn, _lib, raycast
+from ._glue import host as _host, positive as _positive, source_device as _source_device, to_device as _to_device
+from ._gn import A_SLICE, E_INDEX, G_SLICE, N_INDEX, se3_exp, solve_step, unpack  # noqa: F401  (public here)
 
 # struct sgnn_track_pair (include/sgnn_hip.h)
 PAIR_DTYPE = np.dtype([('t', '<f4', (12,)), ('intr_live', '<f4', (4,)), ('intr_model', '<f4', (4,)),
@@ -31,9 +32,6 @@ assert PAIR_DTYPE.itemsize == 96
 
 MAX_BLOCKS = 256            # SGNN_TRACK_MAX_BLOCKS
 MAX_PAIRS = 65535
-# entries of one system (rule 6)
-A_SLICE, G_SLICE, E_INDEX, N_INDEX = slice(0, 21), slice(21, 27), 27, 28
-_TRIU = np.triu_indices(6)
 
 TrackResult = collections.namedtuple('TrackResult', 'pose ok pairs rmse iterations history')
 TrackResult.__doc__ = """What align() found for one frame: pose (4, 4) fp64 cam2world (the guess when ok is false), ok,
@@ -65,16 +63,6 @@ def _intrinsics(k, nb, name):
     return np.ascontiguousarray(k)
 
 
-def _positive(**values):
-    for name, v in values.items():
-        if not (np.float32(v) > 0 and np.isfinite(np.float32(v))):
-            raise ValueError('%s must be positive' % name)
-
-
-def _source_device(x):
-    return _device(x.device if torch.is_tensor(x) and x.is_cuda else None)
-
-
 def pair_table(intrinsics, model_intrinsics, T):
     """Host table of sgnn_track_pair records (rule 1): rows 0..2 of T rounded to fp32 and the two sets of fx, fy, cx,
     cy.  A T that is not finite (in fp64 or after rounding) gets NaN rows: its system stays empty."""
@@ -83,10 +71,7 @@ def pair_table(intrinsics, model_intrinsics, T):
         raise ValueError('T must be (B, 4, 4), got %s' % (t64.shape,))
     nb = t64.shape[0]
     table = np.zeros(nb, dtype=PAIR_DTYPE)
-    with np.errstate(all='ignore'):
-        t = t64[:, :3, :].astype(np.float32)
-    t[~np.isfinite(t).all(axis=(1, 2)) | ~np.isfinite(t64).all(axis=(1, 2))] = np.nan
-    table['t'] = t.reshape(nb, 12)
+    table['t'] = _gn.record_rows(t64[:, :3, :].reshape(nb, 12), np.isfinite(t64[:, 3]).all(axis=1))
     table['intr_live'] = _intrinsics(intrinsics, nb, 'intrinsics')
     table['intr_model'] = _intrinsics(model_intrinsics, nb, 'model intrinsics')
     return table
@@ -116,7 +101,8 @@ def normal_equations(depth, K, model_depth, model_normal, K_model, T, max_dist=0
         raise ValueError('live_normal %s for depth %s' % (tuple(live_normal.shape), (nb, h, w)))
     if nb > MAX_PAIRS:
         raise ValueError('more than %d pairs in one call' % MAX_PAIRS)
-    _positive(max_dist=max_dist, max_angle_deg=max_angle_deg)
+    _positive('max_dist', max_dist)
+    _positive('max_angle_deg', max_angle_deg)
     max_dist2 = np.float32(max_dist) * np.float32(max_dist)             # one fp32 product (rule 4)
     if not (max_dist2 > 0 and np.isfinite(max_dist2)):
         raise ValueError('max_dist = %s is not a usable gate' % max_dist)
@@ -124,33 +110,13 @@ def normal_equations(depth, K, model_depth, model_normal, K_model, T, max_dist=0
     table = pair_table(K, K_model, T)
     if table.shape[0] != nb:
         raise ValueError('%d matrices for %d frames' % (table.shape[0], nb))
-    for name, t, dtype in (('residual', residual, torch.float32), ('assoc', assoc, torch.int32)):
-        if t is not None and not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and
-                                  tuple(t.shape) == (nb, h, w)):
-            raise ValueError('%s must be a contiguous device %s tensor of shape %s' % (name, dtype, (nb, h, w)))
-    out = torch.zeros((nb, 32), dtype=torch.float64, device=dev)
-    if nb == 0:
-        return out
+    _gn.check_per_item((nb, h, w), residual, assoc, 'assoc')
     d = _to_device(depth, torch.float32, dev)
     md = _to_device(model_depth, torch.float32, dev)
     mn = _to_device(model_normal, torch.float32, dev)
     ln = None if live_normal is None else _to_device(live_normal, torch.float32, dev)
-    nblk = min((h * w + 255) // 256, MAX_BLOCKS)
-    ws = torch.empty(nb * nblk * 32, dtype=torch.float64, device=dev)
-    dev_table = torch.from_numpy(table.view(np.uint8)).to(dev)
-    _lib.call('sgnn_track_system', d.data_ptr(), _lib.ptr(ln), h, w, md.data_ptr(), mn.data_ptr(), hm, wm,
-              dev_table.data_ptr(), nb, float(max_dist2), float(cos_min), out.data_ptr(), _lib.ptr(residual),
-              _lib.ptr(assoc), ws.data_ptr(), ws.numel() * 8)
-    return out
-
-
-def unpack(system):
-    """One 32-entry system (host) -> (A (6, 6) symmetric, g (6,), E, N)."""
-    s = np.asarray(system, np.float64).reshape(32)
-    a = np.zeros((6, 6))
-    a[_TRIU] = s[A_SLICE]
-    a = a + np.triu(a, 1).T
-    return a, s[G_SLICE].copy(), float(s[E_INDEX]), int(s[N_INDEX])
+    head = (d.data_ptr(), _lib.ptr(ln), h, w, md.data_ptr(), mn.data_ptr(), hm, wm)
+    return _gn.launch('sgnn_track_system', head, table, (max_dist2, cos_min), h * w, MAX_BLOCKS, (residual, assoc), dev)
 
 
 def level_intrinsics(K):
@@ -166,7 +132,7 @@ def halve(depth, K, delta=0.05):
     has none (rule 9): a depth edge is not blurred into a surface that is not there."""
     dev = _source_device(depth)
     nb, h, w = _frames(depth, 'depth')
-    _positive(delta=delta)
+    _positive('delta', delta)
     k = _host(K, np.float32)
     if k.shape != (4,):
         k = _intrinsics(k, nb, 'intrinsics')
@@ -183,7 +149,7 @@ def depth_normals(depth, K, delta=0.05):
     depth (rule 10)."""
     dev = _source_device(depth)
     nb, h, w = _frames(depth, 'depth')
-    _positive(delta=delta)
+    _positive('delta', delta)
     k = _intrinsics(K, nb, 'intrinsics')
     d = _to_device(depth, torch.float32, dev)
     out = torch.empty((nb, h, w, 3), dtype=torch.float32, device=dev)
@@ -191,44 +157,6 @@ def depth_normals(depth, K, delta=0.05):
         _lib.call('sgnn_track_normals', d.data_ptr(), torch.from_numpy(k).to(dev).data_ptr(), nb, h, w,
                   float(np.float32(delta)), out.data_ptr())
     return out
-
-
-# ---------------------------------------------------------------------------------------------------------
-# the host half (rule 8), fp64
-# ---------------------------------------------------------------------------------------------------------
-def _hat(w):
-    return np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
-
-
-def se3_exp(xi):
-    """Closed-form exponential of the twist xi = (omega, t) -> (4, 4) fp64; the series below |omega| = 1e-8."""
-    xi = np.asarray(xi, np.float64).reshape(6)
-    w, t = xi[:3], xi[3:]
-    th = float(np.linalg.norm(w))
-    k = _hat(w)
-    k2 = k @ k
-    if th < 1e-8:
-        a, b, c = 1.0 - th * th / 6.0, 0.5 - th * th / 24.0, 1.0 / 6.0 - th * th / 120.0
-    else:
-        half = math.sin(0.5 * th)                                        # 1 - cos th = 2 sin^2(th / 2): no cancellation
-        a, b, c = math.sin(th) / th, 2.0 * half * half / (th * th), (th - math.sin(th)) / (th * th * th)
-    out = np.eye(4)
-    out[:3, :3] = np.eye(3) + a * k + b * k2
-    out[:3, 3] = (np.eye(3) + b * k + c * k2) @ t
-    return out
-
-
-def solve_step(system, min_pairs=64):
-    """One 32-entry system (host) -> (xi or None, N, E): A xi = -g by Cholesky; None when N < min_pairs or A is not
-    positive definite."""
-    a, g, e, n = unpack(system)
-    if n < min_pairs or not (np.isfinite(a).all() and np.isfinite(g).all()):
-        return None, n, e
-    try:
-        low = np.linalg.cholesky(a)
-    except np.linalg.LinAlgError:
-        return None, n, e
-    return np.linalg.solve(low.T, np.linalg.solve(low, -g)), n, e
 
 
 def align(depth, K, model_pose, guess_pose, volume, iterations=(10, 5, 4), max_dist=0.1, max_angle_deg=20.0,
@@ -252,10 +180,11 @@ def align(depth, K, model_pose, guess_pose, volume, iterations=(10, 5, 4), max_d
         raise ValueError('iterations = %s' % (iterations,))
     if int(depth.shape[0]) >> (levels - 1) < 1 or int(depth.shape[1]) >> (levels - 1) < 1:
         raise ValueError('a %s frame has no %d levels' % (tuple(depth.shape), levels))
-    _positive(max_dist=max_dist, max_angle_deg=max_angle_deg, delta=delta)
+    for name, v in (('max_dist', max_dist), ('max_angle_deg', max_angle_deg), ('delta', delta)):
+        _positive(name, v)
     model_pose = _host(model_pose, np.float64).reshape(4, 4)
     guess_pose = _host(guess_pose, np.float64).reshape(4, 4)
-    tick = _Timer(timers)
+    tick = _gn.Timer(timers)
     d = [_to_device(depth, torch.float32, dev)[None]]
     k = [_host(K, np.float32).reshape(4)]
     deltas = [np.float32(delta) * np.float32(2 ** lv) for lv in range(levels)]     # the pixel pitch doubles per level
@@ -270,41 +199,18 @@ def align(depth, K, model_pose, guess_pose, volume, iterations=(10, 5, 4), max_d
     tick('cast')
     with np.errstate(all='ignore'):
         T = np.linalg.inv(model_pose) @ guess_pose if np.isfinite(model_pose).all() else np.full((4, 4), np.nan)
-    history, pairs, rmse = [], 0, float('nan')
+    run = _gn.Steps(T[None], min_pairs)
+    history = run.history[0]
     for lv in range(levels - 1, -1, -1):
         for _ in range(int(iterations[lv])):
-            system = normal_equations(d[lv], k[lv], model[lv][0], model[lv][1], k[lv], T[None], max_dist,
-                                      max_angle_deg, live_n[lv]).cpu().numpy()[0]      # 256 bytes
+            systems = normal_equations(d[lv], k[lv], model[lv][0], model[lv][1], k[lv], run.T, max_dist,
+                                       max_angle_deg, live_n[lv]).cpu().numpy()         # 256 bytes
             tick('system')
-            xi, pairs, e = solve_step(system, min_pairs)
-            history.append(pairs)
-            if xi is None:
-                tick('solve')
-                return TrackResult(guess_pose.copy(), False, pairs, float('nan'), len(history), tuple(history))
-            rmse = math.sqrt(e / pairs)
-            T = se3_exp(xi) @ T
+            run.step(systems)
             tick('solve')
-    return TrackResult(model_pose @ T, True, pairs, rmse, len(history), tuple(history))
-
-
-class _Timer(object):
-    """Seconds per stage into a dict, or nothing at all."""
-
-    def __init__(self, sink):
-        self.sink = sink
-        if sink is not None:
-            import time
-            self.clock = time.perf_counter
-            torch.cuda.synchronize()
-            self.last = self.clock()
-
-    def __call__(self, stage):
-        if self.sink is None:
-            return
-        torch.cuda.synchronize()
-        now = self.clock()
-        self.sink[stage] = self.sink.get(stage, 0.0) + (now - self.last)
-        self.last = now
+            if not run.alive[0]:
+                return TrackResult(guess_pose.copy(), False, run.pairs[0], float('nan'), len(history), tuple(history))
+    return TrackResult(model_pose @ run.T[0], True, run.pairs[0], run.rmse[0], len(history), tuple(history))
 
 
 def track_sequence(volume, depth_frames, K, first_pose, integrate=True, timers=None, **align_kwargs):
@@ -321,13 +227,13 @@ def track_sequence(volume, depth_frames, K, first_pose, integrate=True, timers=N
     pose = _host(first_pose, np.float64).reshape(4, 4).copy()
     poses = np.tile(pose, (nf, 1, 1))
     results = []
-    tick = _Timer(timers)
+    tick = _gn.Timer(timers)
     for f in range(nf):
         if f == 0:
             res = TrackResult(pose.copy(), True, 0, 0.0, 0, ())
         else:
             res = align(d[f], k[f], pose, pose, volume, timers=timers, **align_kwargs)
-            tick = _Timer(timers)
+            tick = _gn.Timer(timers)
         results.append(res)
         poses[f] = res.pose
         if res.ok:

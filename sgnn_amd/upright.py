@@ -27,7 +27,9 @@ import numpy as np
 import torch
 
 from . import _lib, fusion, regrid
-from ._glue import device as _device, host as _host, to_device as _to_device
+from ._glue import (host as _host, invertible as _invertible, positive as _gate, source_device as _source_device,
+                    to_device as _to_device)
+from ._gn import record_rows as _record_rows
 
 # struct sgnn_upright_axis (include/sgnn_hip.h)
 AXIS_DTYPE = np.dtype([('u', '<f4', (3,)), ('e1', '<f4', (3,)), ('e2', '<f4', (3,)), ('cos_cone', '<f4'),
@@ -50,13 +52,6 @@ pass, ok, yaw_ok."""
 # ---------------------------------------------------------------------------------------------------------
 # arguments
 # ---------------------------------------------------------------------------------------------------------
-def _gate(name, v):
-    v = np.float32(v)
-    if not (v > 0 and np.isfinite(v)):
-        raise ValueError('%s must be positive' % name)
-    return v
-
-
 def _volume(vol):
     """(sdf, world2grid, voxel_size) of a fusion.TSDFVolume or of such a triple."""
     if isinstance(vol, fusion.TSDFVolume):
@@ -78,9 +73,7 @@ def _check_sdf(sdf):
 def grid_matrices(world2grid):
     """(world2grid, grid2world), each rows 0..2 as (3, 4) fp32: the matrix as given, and its inverse formed in fp64 from
     the fp32 matrix and rounded once (rule S.1)."""
-    w = _host(world2grid, np.float32)
-    if w.shape != (4, 4) or not np.isfinite(w).all() or abs(np.linalg.det(w.astype(np.float64))) == 0:
-        raise ValueError('world2grid must be an invertible (4, 4) matrix')
+    w = _invertible(world2grid, 'world2grid', np.float32)
     with np.errstate(all='ignore'):
         inv = np.linalg.inv(w.astype(np.float64)).astype(np.float32)
     if not np.isfinite(inv).all():
@@ -111,10 +104,7 @@ def axis_table(u, e1, e2, cos_cone, sin_wall):
         raise ValueError('u, e1 and e2 must have the same number of rows')
     c64 = np.broadcast_to(_host(cos_cone, np.float64).reshape(-1), (nb,))
     s64 = np.broadcast_to(_host(sin_wall, np.float64).reshape(-1), (nb,))
-    flat64 = np.concatenate([u64, a64, b64, c64[:, None], s64[:, None]], 1)
-    with np.errstate(all='ignore'):
-        flat = flat64.astype(np.float32)
-    flat[~(np.isfinite(flat).all(1) & np.isfinite(flat64).all(1))] = np.nan
+    flat = _record_rows(np.concatenate([u64, a64, b64, c64[:, None], s64[:, None]], 1))
     table = np.zeros(nb, dtype=AXIS_DTYPE)
     table['u'], table['e1'], table['e2'] = flat[:, 0:3], flat[:, 3:6], flat[:, 6:9]
     table['cos_cone'], table['sin_wall'] = flat[:, 9], flat[:, 10]
@@ -131,7 +121,7 @@ class _Passes(object):
         self.dims = _check_sdf(sdf)
         self.w2g, self.g2w = grid_matrices(world2grid)
         self.band, self.surface = _gate('band', band), _gate('surface', surface)
-        self.dev = _device(sdf.device if torch.is_tensor(sdf) and sdf.is_cuda else None)
+        self.dev = _source_device(sdf)
         self.sdf = _to_device(sdf, torch.float32, self.dev)
 
     def _head(self):

@@ -905,6 +905,25 @@ int sgnn_track_system(const float *depth, const float *live_normal, int h, int w
                       const float *model_normal, int hm, int wm, const sgnn_track_pair *pairs, int npairs,
                       float max_dist2, float cos_min, double *out, float *residual, int32_t *assoc, void *ws,
                       int64_t ws_bytes, sgnn_stream_t stream);
+/* Tracking with colour (rules in INTEGRATION.md section T).
+ * out (n) f32: the intensity (77 R + 150 G + 29 B) / 256 of n R, G, B, A pixels, NaN where A == 0 (rule T1).
+ * n < 2^31 - 256. */
+int sgnn_track_intensity(const uint8_t *rgba, int64_t n, float *out, sgnn_stream_t stream);
+/* out (nframes, h/2, w/2) f32: per 2x2 block the mean intensity of the pixels that sgnn_track_halve averages at the
+ * same delta and whose intensity is not NaN, NaN if none (rule T2).  Sizes as sgnn_track_halve. */
+int sgnn_track_halve_intensity(const float *depth, const float *intensity, int nframes, int h, int w, float delta,
+                               float *out, sgnn_stream_t stream);
+/* out (npairs, 32) f64 in the layout of sgnn_track_system: the photometric system of the live pixels that pass that
+ * call's gates (same pairs, max_dist2, cos_min and live_normal) and rule T3's.  live_intensity (npairs, h, w) and
+ * model_intensity (npairs, hm, wm) f32, NaN = none; max_dist: the gate on the four corner depths, metres;
+ * max_intensity: the gate on |r|.  residual (npairs, h, w) f32 (model minus live intensity, NaN = none) and cell
+ * (npairs, h, w) i32 (y0 * wm + x0 of the bilinear cell, or -1) may be NULL.  Workspace, limits and the fixed order
+ * of the additions as sgnn_track_system. */
+int sgnn_track_color_system(const float *depth, const float *live_normal, const float *live_intensity, int h, int w,
+                            const float *model_depth, const float *model_normal, const float *model_intensity, int hm,
+                            int wm, const sgnn_track_pair *pairs, int npairs, float max_dist2, float cos_min,
+                            float max_dist, float max_intensity, double *out, float *residual, int32_t *cell, void *ws,
+                            int64_t ws_bytes, sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Point sets registered against a volume (sgnn_amd.register; rules in INTEGRATION.md section R): point-to-SDF

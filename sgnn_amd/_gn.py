@@ -109,9 +109,10 @@ class Steps(object):
         self.alive, self.pairs, self.rmse = [True] * nb, [0] * nb, [float('nan')] * nb
         self.history = [[] for _ in range(nb)]
 
-    def step(self, systems):
+    def step(self, systems, geometric=None):
         """systems (B, 32), read back: T <- Exp(xi) . T for every live record.  One that solve_step turns down is dead
-        from here on, with its guess for T and a NaN rmse."""
+        from here on, with its guess for T and a NaN rmse.  geometric: None, or the (B, 32) systems that rmse is taken
+        from when `systems` holds more than their terms (section T rule T6: entry 28 of both is the same N)."""
         for b in range(len(self.alive)):
             if not self.alive[b]:
                 continue
@@ -122,7 +123,7 @@ class Steps(object):
                 self.alive[b], self.rmse[b] = False, float('nan')
                 self.T[b] = self.guess[b]
             else:
-                self.rmse[b] = math.sqrt(e / n)
+                self.rmse[b] = math.sqrt((e if geometric is None else float(geometric[b][E_INDEX])) / n)
                 self.T[b] = se3_exp(xi) @ self.T[b]
 
 

@@ -157,6 +157,10 @@ PROTOTYPES = {
     'sgnn_track_normals': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp]),
     'sgnn_track_system': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_f32, c_f32, c_vp, c_vp,
                                   c_vp, c_vp, c_i64, c_vp]),
+    'sgnn_track_intensity': (c_i32, [c_vp, c_i64, c_vp, c_vp]),
+    'sgnn_track_halve_intensity': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp]),
+    'sgnn_track_color_system': (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_f32,
+                                        c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     'sgnn_register_system': (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_f32, c_f32, c_f32, c_vp, c_vp,
                                      c_vp, c_vp, c_i64, c_vp]),
     'sgnn_upright_histogram': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_f32, c_f32, c_i32, c_vp, c_vp]),

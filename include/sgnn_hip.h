@@ -869,6 +869,27 @@ int sgnn_raycol_cast(const float *sdf, int dx, int dy, int dz, float band, const
                      const sgnn_raycast_frame *frames, int nframes, int chunk, int h, int w, float depth_min, float dt,
                      int nsamples, float *depth, float *normal, int64_t *counters, const uint8_t *colors, uint8_t *rgba,
                      sgnn_stream_t stream);
+/* The differentiable cast (sgnn_amd.raycast.cast_diff; rules in INTEGRATION.md section U).  The forward is
+ * sgnn_raycast_cast without normals and counters, depth bit for bit, and it also writes hit (nframes, h, w) i32, the
+ * sample index k of each pixel's hit (the valid sample <= 0; the previous one is k - 1), -1 = no hit; ok
+ * (nframes, h, w) u8, 1 iff the pixel has a hit whose own cell lies in the volume with eight usable corners; and,
+ * with features (dz, dy, dx, channels) f32, 1 <= channels <= 16, feat (nframes, h, w, channels) f32: the trilinear
+ * weighted sum of all eight corners' features at the hit, 0 where there is no hit or the cell test fails.  features
+ * and feat are both NULL (channels 0) or both given. */
+int sgnn_raygrad_cast(const float *sdf, int dx, int dy, int dz, float band, const uint8_t *bricks,
+                      const sgnn_raycast_frame *frames, int nframes, int chunk, int h, int w, float depth_min, float dt,
+                      int nsamples, const float *features, int channels, float *depth, int32_t *hit, float *feat,
+                      uint8_t *ok, sgnn_stream_t stream);
+/* Its backward: from hit (the forward's record for the same volume, frames and samples) and the incoming gradients
+ * grad_depth (nframes, h, w) and grad_feat (nframes, h, w, channels), either of which may be NULL (zero), ADDS the
+ * gradients into caller-zeroed grad_sdf (dz, dy, dx) and grad_features (dz, dy, dx, channels) with fp32 atomic adds;
+ * either may be NULL (not wanted).  features NULL (channels 0) takes NULL grad_feat and grad_features.  A pixel
+ * without a hit adds nothing and its incoming gradient is not read; a record that names no crossing inside the
+ * volume adds nothing either. */
+int sgnn_raygrad_backward(const float *sdf, int dx, int dy, int dz, const sgnn_raycast_frame *frames, int nframes,
+                          int chunk, int h, int w, float depth_min, float dt, int nsamples, const int32_t *hit,
+                          const float *features, int channels, const float *grad_depth, const float *grad_feat,
+                          float *grad_sdf, float *grad_features, sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Depth frames tracked against a volume (sgnn_amd.track; rules in INTEGRATION.md section I): the "frame to model"

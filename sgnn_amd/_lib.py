@@ -153,6 +153,10 @@ PROTOTYPES = {
                                   c_i32, c_vp, c_vp, c_vp, c_vp]),
     'sgnn_raycol_cast': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32,
                                  c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'sgnn_raygrad_cast': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32,
+                                  c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'sgnn_raygrad_backward': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_i32,
+                                      c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'sgnn_track_halve': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp]),
     'sgnn_track_normals': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp]),
     'sgnn_track_system': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_f32, c_f32, c_vp, c_vp,

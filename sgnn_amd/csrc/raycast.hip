@@ -23,6 +23,15 @@
 // COLOR, rules in INTEGRATION.md section N, restated in tests/raycast_color_ref.py): a lane that has a hit fetches
 // the eight R, G, B, A words of the hit's cell once, after the walk.
 //
+// The differentiable cast (restated in tests/raycast_grad_ref.py) is the same kernel text
+// once more (template parameter DIFF): depth is k_raycast's, and a lane also keeps the sample index of its hit,
+// reads a per-voxel feature vector at the hit and says whether the hit's cell is whole.
+//   k_raycast_grad    the backward: the forward's geometry, one lane per pixel and a wave per 8x8 tile, so a wave's
+//                     atomics fall into few rows of the gradient volumes.  A lane rebuilds both samples of its
+//                     crossing from the recorded index (a sample's position is a product, never a running sum) and
+//                     scatters sixteen terms into grad_sdf and eight per channel into grad_features with
+//                     no-return fp32 atomic adds.
+//
 // Built with -ffp-contract=off (Makefile): every product and sum is rounded on its own.
 #include <math.h>
 #include "common.h"
@@ -92,6 +101,40 @@ __device__ __forceinline__ uint32_t hit_color(const Volume &V, const uint32_t *_
   };
   return ch(__fdiv_rn(n0, s)) | (ch(__fdiv_rn(n1, s)) << 8) | (ch(__fdiv_rn(n2, s)) << 16) | 0xFF000000u;
 }
+
+// offset of corner i of a cell (x fastest, then y, then z) from its corner f, in voxels
+__device__ __forceinline__ int64_t corner_offset(const Volume &V, int i) {
+  return (int64_t)(i >> 2) * V.dx * V.dy + (int64_t)((i >> 1) & 1) * V.dx + (i & 1);
+}
+
+// Section U rule 3: the cell of g and its axis weights {1 - a, a}; false when the cell test fails (NaN fails)
+struct Cell {
+  int64_t base;       // voxel index of corner f
+  float wx[2], wy[2], wz[2];
+  __device__ __forceinline__ float weight(int i) const { return (wz[i >> 2] * wy[(i >> 1) & 1]) * wx[i & 1]; }
+};
+
+__device__ __forceinline__ bool cell_of(const Volume &V, float gx, float gy, float gz, Cell &c) {
+  const float fx = floorf(gx), fy = floorf(gy), fz = floorf(gz);
+  if (!(fx >= 0.f && fx <= (float)(V.dx - 2) && fy >= 0.f && fy <= (float)(V.dy - 2) && fz >= 0.f &&
+        fz <= (float)(V.dz - 2)))
+    return false;
+  c.base = ((int64_t)(int)fz * V.dy + (int)fy) * V.dx + (int)fx;
+  const float ax = gx - fx, ay = gy - fy, az = gz - fz;
+  c.wx[0] = 1.0f - ax, c.wx[1] = ax;
+  c.wy[0] = 1.0f - ay, c.wy[1] = ay;
+  c.wz[0] = 1.0f - az, c.wz[1] = az;
+  return true;
+}
+
+// what k_raycast<.., DIFF = true> reads and writes beside depth
+struct Diff {
+  const float *features;   // (dz, dy, dx, channels), or null
+  int channels;
+  int32_t *hit;            // (F, h, w): the sample index of the hit, -1 = none
+  float *feat;             // (F, h, w, channels), or null
+  uint8_t *ok;             // (F, h, w)
+};
 
 struct Ray {
   float ox, oy, oz;   // origin (grid)
@@ -173,13 +216,14 @@ __device__ __forceinline__ long long wave_sum(long long v) {
   return v;                                        // lane 0 holds the sum
 }
 
-template <bool SKIP, bool NORMALS, bool COLOR>
+template <bool SKIP, bool NORMALS, bool COLOR, bool DIFF>
 __global__ __launch_bounds__(256) void k_raycast(Volume V, const uint8_t *__restrict__ bricks, int nbx, int nby,
                                                 const sgnn_raycast_frame *__restrict__ frames, int f0, int h, int w,
                                                 float depth_min, float dt, int nsamples, float *__restrict__ depth,
                                                 float *__restrict__ normal,
                                                 unsigned long long *__restrict__ counters,
-                                                const uint32_t *__restrict__ colors, uint32_t *__restrict__ rgba) {
+                                                const uint32_t *__restrict__ colors, uint32_t *__restrict__ rgba,
+                                                Diff D) {
   const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
   const int i = (int)blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
   const int j = (int)blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
@@ -268,6 +312,34 @@ __global__ __launch_bounds__(256) void k_raycast(Volume V, const uint8_t *__rest
       if (hit > -INFINITY) c = hit_color(V, colors, R.ox + hit * R.dx, R.oy + hit * R.dy, R.oz + hit * R.dz);
       rgba[px] = c;
     }
+    if (DIFF) {
+      // section U rules 2 and 3: the hit's sample index; features and ok from the cell of the hit, read once
+      const bool has = hit > -INFINITY;
+      D.hit[px] = has ? k : -1;
+      Cell c;
+      const bool cell = has && cell_of(V, R.ox + hit * R.dx, R.oy + hit * R.dy, R.oz + hit * R.dz, c);
+      bool ok = cell;
+      if (cell) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ok = (fabsf(V.sdf[c.base + corner_offset(V, i)]) < V.band) && ok;
+      }
+      D.ok[px] = ok ? 1 : 0;
+      if (D.feat) {
+        float wgt[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) wgt[i] = cell ? c.weight(i) : 0.f;
+        for (int ch = 0; ch < D.channels; ++ch) {
+          float acc = 0.f;
+          if (cell) {
+            const float *p = D.features + c.base * D.channels + ch;
+            acc = wgt[0] * p[0];
+#pragma unroll
+            for (int i = 1; i < 8; ++i) acc = acc + wgt[i] * p[corner_offset(V, i) * D.channels];
+          }
+          D.feat[px * D.channels + ch] = acc;
+        }
+      }
+    }
   }
   if (counters) {                                   // kernel argument: the same for every lane
     const long long e = wave_sum(n_eval), s = wave_sum(n_skip);
@@ -276,6 +348,83 @@ __global__ __launch_bounds__(256) void k_raycast(Volume V, const uint8_t *__rest
       if (s) atomicAdd(counters + 1, (unsigned long long)s);
     }
   }
+}
+
+// Section U rules 4 and 5: the backward of k_raycast<.., DIFF = true>.  hit is the forward's record; a pixel whose
+// record is no sample index of the cast, or whose samples do not lie in cells of the volume (neither happens to a
+// record the forward wrote), adds nothing, so that no record can make a lane write outside the gradient volumes.
+__global__ __launch_bounds__(256) void k_raycast_grad(Volume V, const sgnn_raycast_frame *__restrict__ frames, int f0,
+                                                     int h, int w, float depth_min, float dt, int nsamples,
+                                                     const int32_t *__restrict__ hit,
+                                                     const float *__restrict__ features, int channels,
+                                                     const float *__restrict__ grad_depth,
+                                                     const float *__restrict__ grad_feat, float *__restrict__ grad_sdf,
+                                                     float *__restrict__ grad_features) {
+  const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+  const int i = (int)blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
+  const int j = (int)blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+  const int f = f0 + (int)blockIdx.z;
+  if (!(i < w && j < h)) return;
+  const sgnn_raycast_frame &F = frames[f];
+  const float *G = F.g;
+  const int64_t px = ((int64_t)f * h + j) * w + i;
+  const int k = hit[px];
+  if (!(G[0] == G[0]) || k < 1 || k >= nsamples) return;   // no hit: the incoming gradient is not even read
+  // rule H2
+  const float cx = __fdiv_rn((float)i - F.intr[2], F.intr[0]), cy = __fdiv_rn((float)j - F.intr[3], F.intr[1]);
+  const float dx = (G[0] * cx + G[1] * cy) + G[2], dy = (G[4] * cx + G[5] * cy) + G[6];
+  const float dz = (G[8] * cx + G[9] * cy) + G[10];
+  const float ox = G[3], oy = G[7], oz = G[11];
+  // rules H3 and H4: both samples of the crossing; every finite corner counts, the forward found them usable
+  const float t0 = depth_min + (float)(k - 1) * dt, t1 = depth_min + (float)k * dt;
+  const float g0x = ox + t0 * dx, g0y = oy + t0 * dy, g0z = oz + t0 * dz;
+  const float g1x = ox + t1 * dx, g1y = oy + t1 * dy, g1z = oz + t1 * dz;
+  float pv, v;
+  Cell c0, c1;
+  if (!(sample(V, g0x, g0y, g0z, pv) && sample(V, g1x, g1y, g1z, v))) return;   // V.band is infinite here
+  cell_of(V, g0x, g0y, g0z, c0);
+  cell_of(V, g1x, g1y, g1z, c1);
+  const float den = pv - v;
+  const float ts = t0 + dt * __fdiv_rn(pv, den);     // the forward's depth
+  float Gs = grad_depth ? grad_depth[px] : 0.f;
+  Cell cs;
+  if (grad_feat && cell_of(V, ox + ts * dx, oy + ts * dy, oz + ts * dz, cs)) {
+    float wgt[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) wgt[c] = cs.weight(c);
+    for (int ch = 0; ch < channels; ++ch) {
+      const float gf = grad_feat[px * channels + ch];
+      const int64_t at = cs.base * channels + ch;
+      float q[8];
+#pragma unroll
+      for (int c = 0; c < 8; ++c) q[c] = features[at + corner_offset(V, c) * channels];
+      // the gradient of rule 3's interpolant: four edges along each axis, in corner order
+      float qx = (cs.wz[0] * cs.wy[0]) * (q[1] - q[0]);
+      qx = qx + (cs.wz[0] * cs.wy[1]) * (q[3] - q[2]);
+      qx = qx + (cs.wz[1] * cs.wy[0]) * (q[5] - q[4]);
+      qx = qx + (cs.wz[1] * cs.wy[1]) * (q[7] - q[6]);
+      float qy = (cs.wz[0] * cs.wx[0]) * (q[2] - q[0]);
+      qy = qy + (cs.wz[0] * cs.wx[1]) * (q[3] - q[1]);
+      qy = qy + (cs.wz[1] * cs.wx[0]) * (q[6] - q[4]);
+      qy = qy + (cs.wz[1] * cs.wx[1]) * (q[7] - q[5]);
+      float qz = (cs.wy[0] * cs.wx[0]) * (q[4] - q[0]);
+      qz = qz + (cs.wy[0] * cs.wx[1]) * (q[5] - q[1]);
+      qz = qz + (cs.wy[1] * cs.wx[0]) * (q[6] - q[2]);
+      qz = qz + (cs.wy[1] * cs.wx[1]) * (q[7] - q[3]);
+      Gs = Gs + gf * ((qx * dx + qy * dy) + qz * dz);
+      if (grad_features) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) atomicAdd(grad_features + at + corner_offset(V, c) * channels, gf * wgt[c]);
+      }
+    }
+  }
+  if (!grad_sdf) return;
+  const float A = __fdiv_rn(Gs * dt, den * den);
+  const float cpv = A * (-v), cv = A * pv;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) atomicAdd(grad_sdf + c0.base + corner_offset(V, c), cpv * c0.weight(c));
+#pragma unroll
+  for (int c = 0; c < 8; ++c) atomicAdd(grad_sdf + c1.base + corner_offset(V, c), cv * c1.weight(c));
 }
 
 }  // namespace
@@ -293,17 +442,20 @@ SGNN_EXPORT int sgnn_raycast_bricks(const float *sdf, int dx, int dy, int dz, fl
 
 namespace {
 
-// the launches of both entry points; COLOR: colors (dense R, G, B, A words) is read and rgba written
-template <bool COLOR>
+// the launches of the three forward entry points; COLOR: colors (dense R, G, B, A words) is read and rgba written;
+// DIFF: the recording cast of section U, which has no normals, colours or counters
+template <bool COLOR, bool DIFF>
 int cast(const float *sdf, int dx, int dy, int dz, float band, const uint8_t *bricks, const sgnn_raycast_frame *frames,
          int nframes, int chunk, int h, int w, float depth_min, float dt, int nsamples, float *depth, float *normal,
-         int64_t *counters, const uint8_t *colors, uint8_t *rgba, sgnn_stream_t stream) {
+         int64_t *counters, const uint8_t *colors, uint8_t *rgba, const Diff &D, sgnn_stream_t stream) {
   SGNN_CHECK_ARG(dx >= 1 && dy >= 1 && dz >= 1 && dx <= 65535 && dy <= 65535 && dz <= 65535 && band > 0.f);
   SGNN_CHECK_ARG(nframes >= 0 && h >= 1 && w >= 1 && (int64_t)nframes * h * w < ((int64_t)1 << 31));
   SGNN_CHECK_ARG(dt > 0.f && nsamples >= 1 && nsamples <= (1 << 20));
+  SGNN_CHECK_ARG(!DIFF || (D.features ? D.channels >= 1 && D.channels <= 16 : D.channels == 0));
   if (nframes == 0) return SGNN_OK;
   SGNN_CHECK_ARG(sdf && frames && depth);
   SGNN_CHECK_ARG(!COLOR || (colors && rgba && (((uintptr_t)colors | (uintptr_t)rgba) & 3) == 0));
+  SGNN_CHECK_ARG(!DIFF || (D.hit && D.ok && !D.features == !D.feat));
   const dim3 tiles((w + 15) / 16, (h + 15) / 16);
   SGNN_CHECK_ARG(tiles.y <= 65535);
   if (chunk <= 0 || chunk > nframes) chunk = nframes;
@@ -317,18 +469,18 @@ int cast(const float *sdf, int dx, int dy, int dz, float band, const uint8_t *br
   for (int f0 = 0; f0 < nframes; f0 += chunk) {
     const int f1 = f0 + chunk < nframes ? f0 + chunk : nframes;
     const dim3 grid(tiles.x, tiles.y, f1 - f0);
-    if (bricks && normal)
-      SGNN_LAUNCH((k_raycast<true, true, COLOR>), grid, dim3(256), 0, s, V, bricks, nbx, nby, frames, f0, h, w,
-                  depth_min, dt, nsamples, depth, normal, ctr, cw, pw);
+    if (!DIFF && bricks && normal)
+      SGNN_LAUNCH((k_raycast<true, !DIFF, COLOR, DIFF>), grid, dim3(256), 0, s, V, bricks, nbx, nby, frames, f0, h, w,
+                  depth_min, dt, nsamples, depth, normal, ctr, cw, pw, D);
     else if (bricks)
-      SGNN_LAUNCH((k_raycast<true, false, COLOR>), grid, dim3(256), 0, s, V, bricks, nbx, nby, frames, f0, h, w,
-                  depth_min, dt, nsamples, depth, normal, ctr, cw, pw);
-    else if (normal)
-      SGNN_LAUNCH((k_raycast<false, true, COLOR>), grid, dim3(256), 0, s, V, bricks, nbx, nby, frames, f0, h, w,
-                  depth_min, dt, nsamples, depth, normal, ctr, cw, pw);
+      SGNN_LAUNCH((k_raycast<true, false, COLOR, DIFF>), grid, dim3(256), 0, s, V, bricks, nbx, nby, frames, f0, h, w,
+                  depth_min, dt, nsamples, depth, normal, ctr, cw, pw, D);
+    else if (!DIFF && normal)
+      SGNN_LAUNCH((k_raycast<false, !DIFF, COLOR, DIFF>), grid, dim3(256), 0, s, V, bricks, nbx, nby, frames, f0, h, w,
+                  depth_min, dt, nsamples, depth, normal, ctr, cw, pw, D);
     else
-      SGNN_LAUNCH((k_raycast<false, false, COLOR>), grid, dim3(256), 0, s, V, bricks, nbx, nby, frames, f0, h, w,
-                  depth_min, dt, nsamples, depth, normal, ctr, cw, pw);
+      SGNN_LAUNCH((k_raycast<false, false, COLOR, DIFF>), grid, dim3(256), 0, s, V, bricks, nbx, nby, frames, f0, h, w,
+                  depth_min, dt, nsamples, depth, normal, ctr, cw, pw, D);
     SGNN_CHECK_LAUNCH();
   }
   return SGNN_OK;
@@ -340,14 +492,49 @@ SGNN_EXPORT int sgnn_raycast_cast(const float *sdf, int dx, int dy, int dz, floa
                                   const sgnn_raycast_frame *frames, int nframes, int chunk, int h, int w,
                                   float depth_min, float dt, int nsamples, float *depth, float *normal,
                                   int64_t *counters, sgnn_stream_t stream) {
-  return cast<false>(sdf, dx, dy, dz, band, bricks, frames, nframes, chunk, h, w, depth_min, dt, nsamples, depth,
-                     normal, counters, nullptr, nullptr, stream);
+  return cast<false, false>(sdf, dx, dy, dz, band, bricks, frames, nframes, chunk, h, w, depth_min, dt, nsamples, depth,
+                     normal, counters, nullptr, nullptr, Diff{}, stream);
 }
 
 SGNN_EXPORT int sgnn_raycol_cast(const float *sdf, int dx, int dy, int dz, float band, const uint8_t *bricks,
                                  const sgnn_raycast_frame *frames, int nframes, int chunk, int h, int w,
                                  float depth_min, float dt, int nsamples, float *depth, float *normal,
                                  int64_t *counters, const uint8_t *colors, uint8_t *rgba, sgnn_stream_t stream) {
-  return cast<true>(sdf, dx, dy, dz, band, bricks, frames, nframes, chunk, h, w, depth_min, dt, nsamples, depth,
-                    normal, counters, colors, rgba, stream);
+  return cast<true, false>(sdf, dx, dy, dz, band, bricks, frames, nframes, chunk, h, w, depth_min, dt, nsamples, depth,
+                    normal, counters, colors, rgba, Diff{}, stream);
+}
+
+SGNN_EXPORT int sgnn_raygrad_cast(const float *sdf, int dx, int dy, int dz, float band, const uint8_t *bricks,
+                                  const sgnn_raycast_frame *frames, int nframes, int chunk, int h, int w,
+                                  float depth_min, float dt, int nsamples, const float *features, int channels,
+                                  float *depth, int32_t *hit, float *feat, uint8_t *ok, sgnn_stream_t stream) {
+  return cast<false, true>(sdf, dx, dy, dz, band, bricks, frames, nframes, chunk, h, w, depth_min, dt, nsamples, depth,
+                           nullptr, nullptr, nullptr, nullptr, Diff{features, channels, hit, feat, ok}, stream);
+}
+
+SGNN_EXPORT int sgnn_raygrad_backward(const float *sdf, int dx, int dy, int dz, const sgnn_raycast_frame *frames,
+                                      int nframes, int chunk, int h, int w, float depth_min, float dt, int nsamples,
+                                      const int32_t *hit, const float *features, int channels,
+                                      const float *grad_depth, const float *grad_feat, float *grad_sdf,
+                                      float *grad_features, sgnn_stream_t stream) {
+  SGNN_CHECK_ARG(dx >= 1 && dy >= 1 && dz >= 1 && dx <= 65535 && dy <= 65535 && dz <= 65535);
+  SGNN_CHECK_ARG(nframes >= 0 && h >= 1 && w >= 1 && (int64_t)nframes * h * w < ((int64_t)1 << 31));
+  SGNN_CHECK_ARG(dt > 0.f && nsamples >= 1 && nsamples <= (1 << 20));
+  SGNN_CHECK_ARG(features ? channels >= 1 && channels <= 16 : channels == 0);
+  SGNN_CHECK_ARG(features || (!grad_feat && !grad_features));
+  if (nframes == 0) return SGNN_OK;
+  SGNN_CHECK_ARG(sdf && frames && hit);
+  const dim3 tiles((w + 15) / 16, (h + 15) / 16);
+  SGNN_CHECK_ARG(tiles.y <= 65535);
+  if (!grad_sdf && !(grad_feat && grad_features)) return SGNN_OK;   // nothing to add to
+  if (chunk <= 0 || chunk > nframes) chunk = nframes;
+  if (chunk > 65535) chunk = 65535;
+  const Volume V{sdf, dx, dy, dz, INFINITY};
+  for (int f0 = 0; f0 < nframes; f0 += chunk) {
+    const int f1 = f0 + chunk < nframes ? f0 + chunk : nframes;
+    SGNN_LAUNCH(k_raycast_grad, dim3(tiles.x, tiles.y, f1 - f0), dim3(256), 0, (hipStream_t)stream, V, frames, f0, h, w,
+                depth_min, dt, nsamples, hit, features, channels, grad_depth, grad_feat, grad_sdf, grad_features);
+    SGNN_CHECK_LAUNCH();
+  }
+  return SGNN_OK;
 }

@@ -1015,6 +1015,43 @@ int sgnn_upright_heights(const float *sdf, int dx, int dy, int dz, const float *
                          int32_t *hist, sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * A depth sensor simulated on rendered frames (sgnn_amd.sensor; rules in INTEGRATION.md section V): clean metric
+ * z-depth in, what a structured-light sensor with a horizontal baseline would have returned out.  Frames are (nframes,
+ * h, w) f32 on the device, -inf = no data, at the camera conventions of the blocks above; intrinsics (nframes, 4) f32
+ * on the device: fx, fy, cx, cy per frame, finite, fx and fy not 0 (the caller checks).  nframes * h * w < 2^31;
+ * nframes * h * w == 0 launches nothing and writes nothing.  Every result is a function of the pixel, its frame id and
+ * the seed alone: neither the launch nor the way frames are split over calls shows in any bit.
+ * ------------------------------------------------------------------------- */
+/* the sensor of sgnn_sensor_degrade (48 bytes, read on the host); a stage is off at the value named */
+typedef struct sgnn_sensor_model {
+  float lateral_sigma;     /* V.3: standard deviation in pixels of the lateral jitter, >= 0; 0 = off */
+  float min_depth;         /* V.4: a source depth below min_depth or above max_depth is no data; -inf, +inf = off */
+  float max_depth;
+  float baseline;          /* V.5, V.9: the projector sits at (baseline, 0, 0) in the camera frame, metres; 0 = no
+                              shadow and no disparity steps */
+  float cos_min;           /* V.6: a pixel whose incidence angle has a cosine below cos_min is dropped, [0, 1]; 0 = off */
+  float edge_drop;         /* V.6: the share of edge pixels that are dropped, [0, 1]; 0 = off */
+  float drop;              /* V.7: the share of all pixels that are dropped, [0, 1]; 0 = off */
+  float a0;                /* V.8: sigma = (a0 + a1 (z - a2)^2) (1 + a3 tan^2(incidence)), metres; a0 = a1 = 0 = off */
+  float a1;
+  float a2;
+  float a3;
+  float disparity_quantum; /* V.9: the step of the disparity fx |baseline| / z in pixels, >= 0; 0 = off */
+} sgnn_sensor_model;
+/* mask (nframes, h, w) u8: 1 where a pixel with finite depth > 0 is hidden from the projector by a pixel of its own
+ * row (rule V.5: for baseline > 0, some valid pixel x2 > x has projector column x2 - fx baseline / z2 <= that of x;
+ * for baseline < 0 the mirror image), 0 elsewhere; all 0 for baseline == 0.  baseline finite. */
+int sgnn_sensor_shadow(const float *depth, int nframes, int h, int w, const float *intrinsics, float baseline,
+                       uint8_t *mask, sgnn_stream_t stream);
+/* out (nframes, h, w) f32, not depth itself: rules V.1 - V.9 per pixel.  mask: what sgnn_sensor_shadow wrote for the
+ * same depth, intrinsics and m->baseline; may be NULL when m->baseline == 0.  frame_ids (nframes) i64 on the device:
+ * the frame number that enters the random draws of each frame (rule V.1), NULL = 0 .. nframes - 1.  m: on the host;
+ * a field outside the range its comment names is SGNN_EINVAL. */
+int sgnn_sensor_degrade(const float *depth, const uint8_t *mask, int nframes, int h, int w, const float *intrinsics,
+                        const int64_t *frame_ids, const sgnn_sensor_model *m, uint64_t seed, float *out,
+                        sgnn_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Connected components of volumes and meshes (sgnn_amd.components; rules in INTEGRATION.md section J): lock-free
  * union-find on parent[] (i32, one slot per voxel or vertex; -1 = background / unreferenced).  Larger indices are
  * hooked onto smaller ones, so parent[i] <= i at all times and the root of a finished component is its smallest index.

@@ -11,6 +11,7 @@ Package contents (only what the hot path of SURVEY.md §8 needs):
   track.py     depth frames tracked against a TSDF volume: poses for fusion
   register.py  point sets and volumes registered against a TSDF volume: transforms for regrid.merge (section R)
   upright.py   the gravity-aligned room frame of a scan volume: the transform for regrid.grid_for (section S)
+  sensor.py    a depth sensor simulated on rendered frames: noise, disparity steps, shadow, ragged edges (section V)
 """
 __version__ = '0.1.0'
 
@@ -21,7 +22,7 @@ def __getattr__(name):
     if name == 'bf16_inference':
         from .scn.program import bf16_inference
         return bf16_inference
-    if name in ('track', 'register', 'upright'):   # sgnn_amd.track / .register / .upright without an import statement of their own, as lazily as the above
+    if name in ('track', 'register', 'upright', 'sensor'):   # sgnn_amd.track / .register / .upright / .sensor without an import statement of their own, as lazily as the above
         import importlib
         return importlib.import_module('.' + name, __name__)
     raise AttributeError(name)

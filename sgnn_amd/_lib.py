@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('SGNN_LIB') or os.path.join(_HERE, 'lib', 'libsgnn_hip.so')   # SGNN_LIB: kernel-variant builds (measurements)
 
 c_i32, c_i64, c_f32, c_vp, c_cp = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_char_p
+c_u64 = ctypes.c_uint64
 
 # name -> (restype, argtypes); mirrors include/sgnn_hip.h one to one
 PROTOTYPES = {
@@ -171,6 +172,8 @@ PROTOTYPES = {
     'sgnn_upright_sums': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_f32, c_f32, c_vp, c_i32, c_vp, c_vp]),
     'sgnn_upright_heights': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_f32, c_f32, c_vp, c_f32, c_f32, c_f32, c_i32,
                                      c_vp, c_vp]),
+    'sgnn_sensor_shadow': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_f32, c_vp, c_vp]),
+    'sgnn_sensor_degrade': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_u64, c_vp, c_vp]),
     'sgnn_cc_volume_link': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'sgnn_cc_mesh_link': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
     'sgnn_cc_flatten': (c_i32, [c_vp, c_i64, c_vp, c_vp]),

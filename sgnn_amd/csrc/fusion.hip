@@ -16,8 +16,8 @@
 //   k_fuse_emit_rows      kept voxels -> [z,y,x,0] int64 rows + sdf/vs features (the collated scene input)
 //   k_fuse_known          u8 known codes of the .knw file
 // Compaction between flag and emit is sgnn_compact_mask (stable: raster order, x fastest).  What this file shares with
-// points.hip and regrid.hip is written once in tsdf.h: the OBB test, the affine row, the observation rule (truncation,
-// clamp, weight ramp) and the layout of the colour record.  The per-frame float fold of k_fuse_integrate is its own.
+// points.hip and regrid.hip is written once in tsdf.h: the OBB test, the observation rule (truncation, clamp, weight
+// ramp) and the colour record's layout; the affine row and the projection: geom.h.  The per-frame float fold is its own.
 //
 // Built with -ffp-contract=off (Makefile): every product and sum below is rounded on its own, so the fp32
 // restatement in the tests reproduces sdf, weight, free counter and colour record bit for bit.
@@ -156,8 +156,7 @@ __global__ __launch_bounds__(256) void k_fuse_integrate(float *__restrict__ sdf,
     const bool inbox = eligible && i >= F.box[0] && i <= F.box[1] && j >= F.box[2] && j <= F.box[3];
     const float px3 = tsdf_affine_row(F.m, 0, fi, fj, fk), py3 = tsdf_affine_row(F.m, 1, fi, fj, fk);
     const float pz = tsdf_affine_row(F.m, 2, fi, fj, fk);
-    const float px = __fdiv_rn(px3 * F.intr[0], pz) + F.intr[2];
-    const float py = __fdiv_rn(py3 * F.intr[1], pz) + F.intr[3];
+    const float px = geom_project(F.intr, 0, px3, pz), py = geom_project(F.intr, 1, py3, pz);
     const float rx = roundf(px), ry = roundf(py);                        // NaN / inf fail both range tests
     const bool on_image = inbox && rx >= 0.f && rx < (float)w && ry >= 0.f && ry < (float)h;
     // pixels off the image read at an out-of-range offset: the buffer load returns 0, which fails the range test

@@ -16,7 +16,7 @@
 //                    add for the fixed-point sdf sum, one 64-bit add for (free count << 32 | weight), four more for a
 //                    colour.  Integer sums do not depend on the arrival order: the result has no run-to-run noise.
 //   k_points_fold    one lane per voxel of the box: accumulators -> the volume's running mean, once per call: the fold
-//                    of tsdf.h, as regrid.hip's merge (tsdf.h also has fusion.hip's OBB test, affine map and rule D.5)
+//                    of tsdf.h, as regrid.hip's merge (tsdf.h: also fusion.hip's OBB test and rule D.5; geom.h: the affine map)
 // The accumulators cover the box only: 16 bytes per box voxel, 48 with colour.
 //
 // Built with -ffp-contract=off (Makefile): every product and sum below is rounded on its own.

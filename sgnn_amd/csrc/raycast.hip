@@ -35,6 +35,7 @@
 // Built with -ffp-contract=off (Makefile): every product and sum is rounded on its own.
 #include <math.h>
 #include "common.h"
+#include "geom.h"
 
 namespace {
 
@@ -47,25 +48,21 @@ struct Volume {
 };
 
 // rule 4: the sample at grid position g; false = invalid
-__device__ __forceinline__ bool sample(const Volume &V, float gx, float gy, float gz, float &v) {
-  const float fx = floorf(gx), fy = floorf(gy), fz = floorf(gz);
+__device__ __forceinline__ bool sample(const Volume &V, float gx, float gy, float gz, float &v, GeomCell *cell = nullptr) {
+  GeomCell c;
+  float s[8];
   v = 0.f;
-  if (!(fx >= 0.f && fx <= (float)(V.dx - 2) && fy >= 0.f && fy <= (float)(V.dy - 2) && fz >= 0.f &&
-        fz <= (float)(V.dz - 2)))
-    return false;                                   // NaN fails
-  const int64_t sy = V.dx, sz = (int64_t)V.dx * V.dy;
-  const float *p = V.sdf + ((int64_t)(int)fz * V.dy + (int)fy) * V.dx + (int)fx;
-  const float c000 = p[0], c001 = p[1], c010 = p[sy], c011 = p[sy + 1];
-  const float c100 = p[sz], c101 = p[sz + 1], c110 = p[sz + sy], c111 = p[sz + sy + 1];
+  if (!geom_cell(V.dx, V.dy, V.dz, gx, gy, gz, c)) return false;
+  if (cell) *cell = c;
+  geom_gather(V.sdf + c.base, V.dx, V.dy, s);
   const float b = V.band;                           // |c| < band is false for a NaN and for an infinity
-  if (!(fabsf(c000) < b && fabsf(c001) < b && fabsf(c010) < b && fabsf(c011) < b && fabsf(c100) < b &&
-        fabsf(c101) < b && fabsf(c110) < b && fabsf(c111) < b))
+  if (!(fabsf(s[0]) < b && fabsf(s[1]) < b && fabsf(s[2]) < b && fabsf(s[3]) < b && fabsf(s[4]) < b &&
+        fabsf(s[5]) < b && fabsf(s[6]) < b && fabsf(s[7]) < b))
     return false;
-  const float ax = gx - fx, ay = gy - fy, az = gz - fz;
-  const float x00 = c000 + ax * (c001 - c000), x01 = c010 + ax * (c011 - c010);
-  const float x10 = c100 + ax * (c101 - c100), x11 = c110 + ax * (c111 - c110);
-  const float y0 = x00 + ay * (x01 - x00), y1 = x10 + ay * (x11 - x10);
-  v = y0 + az * (y1 - y0);
+  const float x00 = s[0] + c.a[0] * (s[1] - s[0]), x01 = s[2] + c.a[0] * (s[3] - s[2]);
+  const float x10 = s[4] + c.a[0] * (s[5] - s[4]), x11 = s[6] + c.a[0] * (s[7] - s[6]);
+  const float y0 = x00 + c.a[1] * (x01 - x00), y1 = x10 + c.a[1] * (x11 - x10);
+  v = y0 + c.a[2] * (y1 - y0);
   return true;
 }
 
@@ -73,22 +70,16 @@ __device__ __forceinline__ bool sample(const Volume &V, float gx, float gy, floa
 // pixel as one word, 0 = no colour.  colors is the dense (dz, dy, dx) volume of R, G, B, A words.
 __device__ __forceinline__ uint32_t hit_color(const Volume &V, const uint32_t *__restrict__ colors, float gx, float gy,
                                               float gz) {
-  const float fx = floorf(gx), fy = floorf(gy), fz = floorf(gz);
-  if (!(fx >= 0.f && fx <= (float)(V.dx - 2) && fy >= 0.f && fy <= (float)(V.dy - 2) && fz >= 0.f &&
-        fz <= (float)(V.dz - 2)))
-    return 0u;
-  const int64_t sy = V.dx, sz = (int64_t)V.dx * V.dy;
-  const uint32_t *p = colors + ((int64_t)(int)fz * V.dy + (int)fy) * V.dx + (int)fx;
-  uint32_t c[8];                                    // x fastest, then y, then z
-#pragma unroll
-  for (int i = 0; i < 8; ++i) c[i] = p[(i >> 2) * sz + ((i >> 1) & 1) * sy + (i & 1)];
-  const float ax = gx - fx, ay = gy - fy, az = gz - fz;
-  const float wx[2] = {1.0f - ax, ax}, wy[2] = {1.0f - ay, ay}, wz[2] = {1.0f - az, az};
+  GeomCell cell;
+  if (!geom_cell(V.dx, V.dy, V.dz, gx, gy, gz, cell)) return 0u;
+  uint32_t c[8];
+  geom_gather(colors + cell.base, V.dx, V.dy, c);
+  const GeomWeights W(cell.a);
   float s = 0.f, n0 = 0.f, n1 = 0.f, n2 = 0.f;
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     // a corner without a colour adds a weight of zero: the sums are those over the counted corners, bit for bit
-    const float w = (c[i] >> 24) ? (wz[i >> 2] * wy[(i >> 1) & 1]) * wx[i & 1] : 0.f;
+    const float w = (c[i] >> 24) ? W.corner(i) : 0.f;
     s = s + w;
     n0 = n0 + w * (float)(c[i] & 255u);
     n1 = n1 + w * (float)((c[i] >> 8) & 255u);
@@ -100,31 +91,6 @@ __device__ __forceinline__ uint32_t hit_color(const Volume &V, const uint32_t *_
     return r >= 255.0f ? 255u : (r >= 0.0f ? (uint32_t)r : 0u);
   };
   return ch(__fdiv_rn(n0, s)) | (ch(__fdiv_rn(n1, s)) << 8) | (ch(__fdiv_rn(n2, s)) << 16) | 0xFF000000u;
-}
-
-// offset of corner i of a cell (x fastest, then y, then z) from its corner f, in voxels
-__device__ __forceinline__ int64_t corner_offset(const Volume &V, int i) {
-  return (int64_t)(i >> 2) * V.dx * V.dy + (int64_t)((i >> 1) & 1) * V.dx + (i & 1);
-}
-
-// Section U rule 3: the cell of g and its axis weights {1 - a, a}; false when the cell test fails (NaN fails)
-struct Cell {
-  int64_t base;       // voxel index of corner f
-  float wx[2], wy[2], wz[2];
-  __device__ __forceinline__ float weight(int i) const { return (wz[i >> 2] * wy[(i >> 1) & 1]) * wx[i & 1]; }
-};
-
-__device__ __forceinline__ bool cell_of(const Volume &V, float gx, float gy, float gz, Cell &c) {
-  const float fx = floorf(gx), fy = floorf(gy), fz = floorf(gz);
-  if (!(fx >= 0.f && fx <= (float)(V.dx - 2) && fy >= 0.f && fy <= (float)(V.dy - 2) && fz >= 0.f &&
-        fz <= (float)(V.dz - 2)))
-    return false;
-  c.base = ((int64_t)(int)fz * V.dy + (int)fy) * V.dx + (int)fx;
-  const float ax = gx - fx, ay = gy - fy, az = gz - fz;
-  c.wx[0] = 1.0f - ax, c.wx[1] = ax;
-  c.wy[0] = 1.0f - ay, c.wy[1] = ay;
-  c.wz[0] = 1.0f - az, c.wz[1] = az;
-  return true;
 }
 
 // what k_raycast<.., DIFF = true> reads and writes beside depth
@@ -141,6 +107,20 @@ struct Ray {
   float dx, dy, dz;   // direction per unit of z-depth (grid)
   float t0, dt;       // sample k sits at t0 + (float)k * dt
 };
+
+// the pixel of a lane: a block covers 16x16 pixels, each of its four waves an 8x8 tile
+__device__ __forceinline__ void lane_pixel(int &i, int &j) {
+  const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+  i = (int)blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
+  j = (int)blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+}
+
+// rule 2: the ray of pixel (i, j) of a frame; its direction is the pose's linear part of (cx, cy, 1)
+__device__ __forceinline__ Ray pixel_ray(const sgnn_raycast_frame &F, int i, int j, float depth_min, float dt) {
+  const float cx = geom_unproject(F.intr, 0, (float)i), cy = geom_unproject(F.intr, 1, (float)j);
+  return Ray{F.g[3], F.g[7], F.g[11], geom_linear_row(F.g, 0, cx, cy, 1.0f), geom_linear_row(F.g, 1, cx, cy, 1.0f),
+             geom_linear_row(F.g, 2, cx, cy, 1.0f), depth_min, dt};   // a product with 1 is exact
+}
 
 // the first sample at or after depth tc, less one: where a jump that started before tc has to stop (k + 1 at least)
 __device__ __forceinline__ int jump_target(const Ray &R, float tc, int k, int n) {
@@ -224,25 +204,14 @@ __global__ __launch_bounds__(256) void k_raycast(Volume V, const uint8_t *__rest
                                                 unsigned long long *__restrict__ counters,
                                                 const uint32_t *__restrict__ colors, uint32_t *__restrict__ rgba,
                                                 Diff D) {
-  const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
-  const int i = (int)blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
-  const int j = (int)blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+  int i, j;
+  lane_pixel(i, j);
   const int f = f0 + (int)blockIdx.z;
   const sgnn_raycast_frame &F = frames[f];
   const float *G = F.g;
   const bool pixel = i < w && j < h;
   const bool live = pixel && G[0] == G[0];          // non-finite pose (the host stores NaN): the frame stays empty
-  // rule 2
-  const float cx = __fdiv_rn((float)i - F.intr[2], F.intr[0]), cy = __fdiv_rn((float)j - F.intr[3], F.intr[1]);
-  Ray R;
-  R.dx = (G[0] * cx + G[1] * cy) + G[2];
-  R.dy = (G[4] * cx + G[5] * cy) + G[6];
-  R.dz = (G[8] * cx + G[9] * cy) + G[10];
-  R.ox = G[3];
-  R.oy = G[7];
-  R.oz = G[11];
-  R.t0 = depth_min;
-  R.dt = dt;
+  const Ray R = pixel_ray(F, i, j, depth_min, dt);
   // rules 3-5
   const int n = live ? nsamples : 0;
   int k = 0, n_eval = 0, n_skip = 0;
@@ -279,7 +248,7 @@ __global__ __launch_bounds__(256) void k_raycast(Volume V, const uint8_t *__rest
     depth[px] = hit;
     if (NORMALS) {
       // rule 6
-      float nx = NAN, ny = NAN, nz = NAN;
+      float n[3] = {NAN, NAN, NAN};
       if (hit > -INFINITY) {
         const float gx = R.ox + hit * R.dx, gy = R.oy + hit * R.dy, gz = R.oz + hit * R.dz;
         float xp, xm, yp, ym, zp, zm;
@@ -291,20 +260,12 @@ __global__ __launch_bounds__(256) void k_raycast(Volume V, const uint8_t *__rest
         ok = sample(V, gx, gy, gz - 0.5f, zm) && ok;
         if (ok) {
           const float a = xp - xm, b = yp - ym, c = zp - zm;
-          const float qx = (G[0] * a + G[4] * b) + G[8] * c;
-          const float qy = (G[1] * a + G[5] * b) + G[9] * c;
-          const float qz = (G[2] * a + G[6] * b) + G[10] * c;
-          const float len = (float)sqrt((double)((qx * qx + qy * qy) + qz * qz));   // correctly rounded
-          if (len > 0.f && len < INFINITY) {
-            nx = __fdiv_rn(qx, len);
-            ny = __fdiv_rn(qy, len);
-            nz = __fdiv_rn(qz, len);
-          }
+          geom_unit(geom_linear_col(G, 0, a, b, c), geom_linear_col(G, 1, a, b, c), geom_linear_col(G, 2, a, b, c), n);
         }
       }
-      normal[px * 3 + 0] = nx;
-      normal[px * 3 + 1] = ny;
-      normal[px * 3 + 2] = nz;
+      normal[px * 3 + 0] = n[0];
+      normal[px * 3 + 1] = n[1];
+      normal[px * 3 + 2] = n[2];
     }
     if (COLOR) {
       // section N: only a lane with a hit fetches colour, at the point of rule 6
@@ -316,25 +277,25 @@ __global__ __launch_bounds__(256) void k_raycast(Volume V, const uint8_t *__rest
       // section U rules 2 and 3: the hit's sample index; features and ok from the cell of the hit, read once
       const bool has = hit > -INFINITY;
       D.hit[px] = has ? k : -1;
-      Cell c;
-      const bool cell = has && cell_of(V, R.ox + hit * R.dx, R.oy + hit * R.dy, R.oz + hit * R.dz, c);
+      GeomCell c;
+      const bool cell = has && geom_cell(V.dx, V.dy, V.dz, R.ox + hit * R.dx, R.oy + hit * R.dy, R.oz + hit * R.dz, c);
       bool ok = cell;
       if (cell) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) ok = (fabsf(V.sdf[c.base + corner_offset(V, i)]) < V.band) && ok;
+        for (int i = 0; i < 8; ++i) ok = (fabsf(V.sdf[c.base + geom_corner(V.dx, V.dy, i)]) < V.band) && ok;
       }
       D.ok[px] = ok ? 1 : 0;
       if (D.feat) {
         float wgt[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) wgt[i] = cell ? c.weight(i) : 0.f;
+        for (int i = 0; i < 8; ++i) wgt[i] = cell ? GeomWeights(c.a).corner(i) : 0.f;
         for (int ch = 0; ch < D.channels; ++ch) {
           float acc = 0.f;
-          if (cell) {
+          if (cell) {   // straight from the loads, corner by corner: a gather into registers first costs VGPRs here
             const float *p = D.features + c.base * D.channels + ch;
             acc = wgt[0] * p[0];
 #pragma unroll
-            for (int i = 1; i < 8; ++i) acc = acc + wgt[i] * p[corner_offset(V, i) * D.channels];
+            for (int i = 1; i < 8; ++i) acc = acc + wgt[i] * p[geom_corner(V.dx, V.dy, i) * D.channels];
           }
           D.feat[px * D.channels + ch] = acc;
         }
@@ -343,7 +304,7 @@ __global__ __launch_bounds__(256) void k_raycast(Volume V, const uint8_t *__rest
   }
   if (counters) {                                   // kernel argument: the same for every lane
     const long long e = wave_sum(n_eval), s = wave_sum(n_skip);
-    if (lane == 0) {
+    if ((threadIdx.x & 63) == 0) {                  // lane 0
       if (e) atomicAdd(counters + 0, (unsigned long long)e);
       if (s) atomicAdd(counters + 1, (unsigned long long)s);
     }
@@ -360,61 +321,51 @@ __global__ __launch_bounds__(256) void k_raycast_grad(Volume V, const sgnn_rayca
                                                      const float *__restrict__ grad_depth,
                                                      const float *__restrict__ grad_feat, float *__restrict__ grad_sdf,
                                                      float *__restrict__ grad_features) {
-  const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
-  const int i = (int)blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
-  const int j = (int)blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+  int i, j;
+  lane_pixel(i, j);
   const int f = f0 + (int)blockIdx.z;
   if (!(i < w && j < h)) return;
   const sgnn_raycast_frame &F = frames[f];
-  const float *G = F.g;
   const int64_t px = ((int64_t)f * h + j) * w + i;
   const int k = hit[px];
-  if (!(G[0] == G[0]) || k < 1 || k >= nsamples) return;   // no hit: the incoming gradient is not even read
-  // rule H2
-  const float cx = __fdiv_rn((float)i - F.intr[2], F.intr[0]), cy = __fdiv_rn((float)j - F.intr[3], F.intr[1]);
-  const float dx = (G[0] * cx + G[1] * cy) + G[2], dy = (G[4] * cx + G[5] * cy) + G[6];
-  const float dz = (G[8] * cx + G[9] * cy) + G[10];
-  const float ox = G[3], oy = G[7], oz = G[11];
+  if (!(F.g[0] == F.g[0]) || k < 1 || k >= nsamples) return;   // no hit: the incoming gradient is not even read
+  const Ray R = pixel_ray(F, i, j, depth_min, dt);               // rule H2
   // rules H3 and H4: both samples of the crossing; every finite corner counts, the forward found them usable
-  const float t0 = depth_min + (float)(k - 1) * dt, t1 = depth_min + (float)k * dt;
-  const float g0x = ox + t0 * dx, g0y = oy + t0 * dy, g0z = oz + t0 * dz;
-  const float g1x = ox + t1 * dx, g1y = oy + t1 * dy, g1z = oz + t1 * dz;
+  const float t0 = R.t0 + (float)(k - 1) * R.dt, t1 = R.t0 + (float)k * R.dt;
   float pv, v;
-  Cell c0, c1;
-  if (!(sample(V, g0x, g0y, g0z, pv) && sample(V, g1x, g1y, g1z, v))) return;   // V.band is infinite here
-  cell_of(V, g0x, g0y, g0z, c0);
-  cell_of(V, g1x, g1y, g1z, c1);
+  GeomCell c0, c1;                                    // V.band is infinite here
+  if (!(sample(V, R.ox + t0 * R.dx, R.oy + t0 * R.dy, R.oz + t0 * R.dz, pv, &c0) &&
+        sample(V, R.ox + t1 * R.dx, R.oy + t1 * R.dy, R.oz + t1 * R.dz, v, &c1)))
+    return;
   const float den = pv - v;
   const float ts = t0 + dt * __fdiv_rn(pv, den);     // the forward's depth
   float Gs = grad_depth ? grad_depth[px] : 0.f;
-  Cell cs;
-  if (grad_feat && cell_of(V, ox + ts * dx, oy + ts * dy, oz + ts * dz, cs)) {
-    float wgt[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) wgt[c] = cs.weight(c);
+  GeomCell cs;
+  if (grad_feat && geom_cell(V.dx, V.dy, V.dz, R.ox + ts * R.dx, R.oy + ts * R.dy, R.oz + ts * R.dz, cs)) {
+    const GeomWeights W(cs.a);
     for (int ch = 0; ch < channels; ++ch) {
       const float gf = grad_feat[px * channels + ch];
       const int64_t at = cs.base * channels + ch;
       float q[8];
-#pragma unroll
-      for (int c = 0; c < 8; ++c) q[c] = features[at + corner_offset(V, c) * channels];
-      // the gradient of rule 3's interpolant: four edges along each axis, in corner order
-      float qx = (cs.wz[0] * cs.wy[0]) * (q[1] - q[0]);
-      qx = qx + (cs.wz[0] * cs.wy[1]) * (q[3] - q[2]);
-      qx = qx + (cs.wz[1] * cs.wy[0]) * (q[5] - q[4]);
-      qx = qx + (cs.wz[1] * cs.wy[1]) * (q[7] - q[6]);
-      float qy = (cs.wz[0] * cs.wx[0]) * (q[2] - q[0]);
-      qy = qy + (cs.wz[0] * cs.wx[1]) * (q[3] - q[1]);
-      qy = qy + (cs.wz[1] * cs.wx[0]) * (q[6] - q[4]);
-      qy = qy + (cs.wz[1] * cs.wx[1]) * (q[7] - q[5]);
-      float qz = (cs.wy[0] * cs.wx[0]) * (q[4] - q[0]);
-      qz = qz + (cs.wy[0] * cs.wx[1]) * (q[5] - q[1]);
-      qz = qz + (cs.wy[1] * cs.wx[0]) * (q[6] - q[2]);
-      qz = qz + (cs.wy[1] * cs.wx[1]) * (q[7] - q[3]);
-      Gs = Gs + gf * ((qx * dx + qy * dy) + qz * dz);
+      geom_gather(features + at, V.dx, V.dy, q, channels);
+      // the gradient of rule 3's interpolant in its weight form (register.hip's rule 4 lerps and rounds differently)
+      float qx = (W.z[0] * W.y[0]) * (q[1] - q[0]);
+      qx = qx + (W.z[0] * W.y[1]) * (q[3] - q[2]);
+      qx = qx + (W.z[1] * W.y[0]) * (q[5] - q[4]);
+      qx = qx + (W.z[1] * W.y[1]) * (q[7] - q[6]);
+      float qy = (W.z[0] * W.x[0]) * (q[2] - q[0]);
+      qy = qy + (W.z[0] * W.x[1]) * (q[3] - q[1]);
+      qy = qy + (W.z[1] * W.x[0]) * (q[6] - q[4]);
+      qy = qy + (W.z[1] * W.x[1]) * (q[7] - q[5]);
+      float qz = (W.y[0] * W.x[0]) * (q[4] - q[0]);
+      qz = qz + (W.y[0] * W.x[1]) * (q[5] - q[1]);
+      qz = qz + (W.y[1] * W.x[0]) * (q[6] - q[2]);
+      qz = qz + (W.y[1] * W.x[1]) * (q[7] - q[3]);
+      Gs = Gs + gf * ((qx * R.dx + qy * R.dy) + qz * R.dz);
       if (grad_features) {
 #pragma unroll
-        for (int c = 0; c < 8; ++c) atomicAdd(grad_features + at + corner_offset(V, c) * channels, gf * wgt[c]);
+        for (int c = 0; c < 8; ++c)
+          atomicAdd(grad_features + at + geom_corner(V.dx, V.dy, c) * channels, gf * W.corner(c));
       }
     }
   }
@@ -422,9 +373,9 @@ __global__ __launch_bounds__(256) void k_raycast_grad(Volume V, const sgnn_rayca
   const float A = __fdiv_rn(Gs * dt, den * den);
   const float cpv = A * (-v), cv = A * pv;
 #pragma unroll
-  for (int c = 0; c < 8; ++c) atomicAdd(grad_sdf + c0.base + corner_offset(V, c), cpv * c0.weight(c));
+  for (int c = 0; c < 8; ++c) atomicAdd(grad_sdf + c0.base + geom_corner(V.dx, V.dy, c), cpv * GeomWeights(c0.a).corner(c));
 #pragma unroll
-  for (int c = 0; c < 8; ++c) atomicAdd(grad_sdf + c1.base + corner_offset(V, c), cv * c1.weight(c));
+  for (int c = 0; c < 8; ++c) atomicAdd(grad_sdf + c1.base + geom_corner(V.dx, V.dy, c), cv * GeomWeights(c1.a).corner(c));
 }
 
 }  // namespace
@@ -442,48 +393,56 @@ SGNN_EXPORT int sgnn_raycast_bricks(const float *sdf, int dx, int dy, int dz, fl
 
 namespace {
 
+// what the forward entrances and the backward check alike; tiles: the 16x16 pixel blocks of a frame (no frames, no launch)
+int frames_arg(int dx, int dy, int dz, int nframes, int h, int w, float dt, int nsamples, const float *features,
+               int channels, dim3 &tiles) {
+  SGNN_CHECK_ARG(dx >= 1 && dy >= 1 && dz >= 1 && dx <= 65535 && dy <= 65535 && dz <= 65535);
+  SGNN_CHECK_ARG(nframes >= 0 && h >= 1 && w >= 1 && (int64_t)nframes * h * w < ((int64_t)1 << 31));
+  SGNN_CHECK_ARG(dt > 0.f && nsamples >= 1 && nsamples <= (1 << 20));
+  SGNN_CHECK_ARG(features ? channels >= 1 && channels <= 16 : channels == 0);
+  tiles = dim3((w + 15) / 16, (h + 15) / 16);
+  SGNN_CHECK_ARG(nframes == 0 || tiles.y <= 65535);
+  return SGNN_OK;
+}
+
+// launch(f0, n) for the frames f0 .. f0 + n - 1 of every chunk; a chunk is one launch and at most 65535 frames
+template <typename L>
+int for_frame_chunks(int nframes, int chunk, L launch) {
+  if (chunk <= 0 || chunk > nframes) chunk = nframes;
+  if (chunk > 65535) chunk = 65535;
+  for (int f0 = 0; f0 < nframes; f0 += chunk) {
+    launch(f0, (f0 + chunk < nframes ? f0 + chunk : nframes) - f0);
+    SGNN_CHECK_LAUNCH();
+  }
+  return SGNN_OK;
+}
+
 // the launches of the three forward entry points; COLOR: colors (dense R, G, B, A words) is read and rgba written;
 // DIFF: the recording cast of section U, which has no normals, colours or counters
 template <bool COLOR, bool DIFF>
 int cast(const float *sdf, int dx, int dy, int dz, float band, const uint8_t *bricks, const sgnn_raycast_frame *frames,
          int nframes, int chunk, int h, int w, float depth_min, float dt, int nsamples, float *depth, float *normal,
          int64_t *counters, const uint8_t *colors, uint8_t *rgba, const Diff &D, sgnn_stream_t stream) {
-  SGNN_CHECK_ARG(dx >= 1 && dy >= 1 && dz >= 1 && dx <= 65535 && dy <= 65535 && dz <= 65535 && band > 0.f);
-  SGNN_CHECK_ARG(nframes >= 0 && h >= 1 && w >= 1 && (int64_t)nframes * h * w < ((int64_t)1 << 31));
-  SGNN_CHECK_ARG(dt > 0.f && nsamples >= 1 && nsamples <= (1 << 20));
-  SGNN_CHECK_ARG(!DIFF || (D.features ? D.channels >= 1 && D.channels <= 16 : D.channels == 0));
+  dim3 tiles;
+  if (const int rc = frames_arg(dx, dy, dz, nframes, h, w, dt, nsamples, D.features, D.channels, tiles)) return rc;
+  SGNN_CHECK_ARG(band > 0.f);
   if (nframes == 0) return SGNN_OK;
   SGNN_CHECK_ARG(sdf && frames && depth);
   SGNN_CHECK_ARG(!COLOR || (colors && rgba && (((uintptr_t)colors | (uintptr_t)rgba) & 3) == 0));
   SGNN_CHECK_ARG(!DIFF || (D.hit && D.ok && !D.features == !D.feat));
-  const dim3 tiles((w + 15) / 16, (h + 15) / 16);
-  SGNN_CHECK_ARG(tiles.y <= 65535);
-  if (chunk <= 0 || chunk > nframes) chunk = nframes;
-  if (chunk > 65535) chunk = 65535;
   const Volume V{sdf, dx, dy, dz, band};
   const int nbx = (dx + BRICK - 1) / BRICK, nby = (dy + BRICK - 1) / BRICK;
-  unsigned long long *ctr = reinterpret_cast<unsigned long long *>(counters);
-  const uint32_t *cw = reinterpret_cast<const uint32_t *>(colors);
-  uint32_t *pw = reinterpret_cast<uint32_t *>(rgba);
-  hipStream_t s = (hipStream_t)stream;
-  for (int f0 = 0; f0 < nframes; f0 += chunk) {
-    const int f1 = f0 + chunk < nframes ? f0 + chunk : nframes;
-    const dim3 grid(tiles.x, tiles.y, f1 - f0);
-    if (!DIFF && bricks && normal)
-      SGNN_LAUNCH((k_raycast<true, !DIFF, COLOR, DIFF>), grid, dim3(256), 0, s, V, bricks, nbx, nby, frames, f0, h, w,
-                  depth_min, dt, nsamples, depth, normal, ctr, cw, pw, D);
-    else if (bricks)
-      SGNN_LAUNCH((k_raycast<true, false, COLOR, DIFF>), grid, dim3(256), 0, s, V, bricks, nbx, nby, frames, f0, h, w,
-                  depth_min, dt, nsamples, depth, normal, ctr, cw, pw, D);
-    else if (!DIFF && normal)
-      SGNN_LAUNCH((k_raycast<false, !DIFF, COLOR, DIFF>), grid, dim3(256), 0, s, V, bricks, nbx, nby, frames, f0, h, w,
-                  depth_min, dt, nsamples, depth, normal, ctr, cw, pw, D);
-    else
-      SGNN_LAUNCH((k_raycast<false, false, COLOR, DIFF>), grid, dim3(256), 0, s, V, bricks, nbx, nby, frames, f0, h, w,
-                  depth_min, dt, nsamples, depth, normal, ctr, cw, pw, D);
-    SGNN_CHECK_LAUNCH();
-  }
-  return SGNN_OK;
+  return for_frame_chunks(nframes, chunk, [&](int f0, int n) {
+    auto go = [&](auto kernel) {
+      SGNN_LAUNCH(kernel, dim3(tiles.x, tiles.y, n), dim3(256), 0, (hipStream_t)stream, V, bricks, nbx, nby, frames, f0,
+                  h, w, depth_min, dt, nsamples, depth, normal, reinterpret_cast<unsigned long long *>(counters),
+                  reinterpret_cast<const uint32_t *>(colors), reinterpret_cast<uint32_t *>(rgba), D);
+    };
+    if (!DIFF && bricks && normal) go(k_raycast<true, !DIFF, COLOR, DIFF>);
+    else if (bricks) go(k_raycast<true, false, COLOR, DIFF>);
+    else if (!DIFF && normal) go(k_raycast<false, !DIFF, COLOR, DIFF>);
+    else go(k_raycast<false, false, COLOR, DIFF>);
+  });
 }
 
 }  // namespace
@@ -517,24 +476,15 @@ SGNN_EXPORT int sgnn_raygrad_backward(const float *sdf, int dx, int dy, int dz, 
                                       const int32_t *hit, const float *features, int channels,
                                       const float *grad_depth, const float *grad_feat, float *grad_sdf,
                                       float *grad_features, sgnn_stream_t stream) {
-  SGNN_CHECK_ARG(dx >= 1 && dy >= 1 && dz >= 1 && dx <= 65535 && dy <= 65535 && dz <= 65535);
-  SGNN_CHECK_ARG(nframes >= 0 && h >= 1 && w >= 1 && (int64_t)nframes * h * w < ((int64_t)1 << 31));
-  SGNN_CHECK_ARG(dt > 0.f && nsamples >= 1 && nsamples <= (1 << 20));
-  SGNN_CHECK_ARG(features ? channels >= 1 && channels <= 16 : channels == 0);
+  dim3 tiles;
+  if (const int rc = frames_arg(dx, dy, dz, nframes, h, w, dt, nsamples, features, channels, tiles)) return rc;
   SGNN_CHECK_ARG(features || (!grad_feat && !grad_features));
   if (nframes == 0) return SGNN_OK;
   SGNN_CHECK_ARG(sdf && frames && hit);
-  const dim3 tiles((w + 15) / 16, (h + 15) / 16);
-  SGNN_CHECK_ARG(tiles.y <= 65535);
   if (!grad_sdf && !(grad_feat && grad_features)) return SGNN_OK;   // nothing to add to
-  if (chunk <= 0 || chunk > nframes) chunk = nframes;
-  if (chunk > 65535) chunk = 65535;
   const Volume V{sdf, dx, dy, dz, INFINITY};
-  for (int f0 = 0; f0 < nframes; f0 += chunk) {
-    const int f1 = f0 + chunk < nframes ? f0 + chunk : nframes;
-    SGNN_LAUNCH(k_raycast_grad, dim3(tiles.x, tiles.y, f1 - f0), dim3(256), 0, (hipStream_t)stream, V, frames, f0, h, w,
+  return for_frame_chunks(nframes, chunk, [&](int f0, int n) {
+    SGNN_LAUNCH(k_raycast_grad, dim3(tiles.x, tiles.y, n), dim3(256), 0, (hipStream_t)stream, V, frames, f0, h, w,
                 depth_min, dt, nsamples, hit, features, channels, grad_depth, grad_feat, grad_sdf, grad_features);
-    SGNN_CHECK_LAUNCH();
-  }
-  return SGNN_OK;
+  });
 }

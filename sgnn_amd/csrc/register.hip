@@ -16,7 +16,7 @@
 #include <math.h>
 #include "common.h"
 #include "gn_system.h"
-#include "tsdf.h"
+#include "geom.h"
 
 namespace {
 
@@ -48,7 +48,8 @@ __global__ __launch_bounds__(BLOCK) void k_register_system(const float *__restri
     tsdf_affine(W, q[0], q[1], q[2], g);
     bool ok = rec_ok && finite_f(px) && finite_f(py) && finite_f(pz) && finite_f(q[0]) && finite_f(q[1]) &&
               finite_f(q[2]) && finite_f(g[0]) && finite_f(g[1]) && finite_f(g[2]);
-    // rule 3: the cell and its 8 corners; a lane without a cell reads cell 0, which every volume has (dims >= 2)
+    // rule 3: the cell and its 8 corners; a lane without a cell reads cell 0, which every volume has (dims >= 2).
+    // Written out, not on geom.h's cell helpers: their array form compiled worse here, and speed wins over sharing.
     const float fx = floorf(g[0]), fy = floorf(g[1]), fz = floorf(g[2]);
     ok = ok && fx >= 0.f && fx <= (float)(dx - 2) && fy >= 0.f && fy <= (float)(dy - 2) && fz >= 0.f &&
          fz <= (float)(dz - 2);
@@ -65,9 +66,8 @@ __global__ __launch_bounds__(BLOCK) void k_register_system(const float *__restri
     const float gx = lerp(lerp(c001 - c000, c011 - c010, ay), lerp(c101 - c100, c111 - c110, ay), az);
     const float gy = lerp(lerp(c010 - c000, c011 - c001, ax), lerp(c110 - c100, c111 - c101, ax), az);
     const float gz = lerp(lerp(c100 - c000, c101 - c001, ax), lerp(c110 - c010, c111 - c011, ax), ay);
-    const float nx = (W[0] * gx + W[4] * gy) + W[8] * gz;
-    const float ny = (W[1] * gx + W[5] * gy) + W[9] * gz;
-    const float nz = (W[2] * gx + W[6] * gy) + W[10] * gz;
+    const float nx = geom_linear_col(W, 0, gx, gy, gz), ny = geom_linear_col(W, 1, gx, gy, gz);
+    const float nz = geom_linear_col(W, 2, gx, gy, gz);
     // rule 5
     const float len2 = (nx * nx + ny * ny) + nz * nz;
     ok = ok && fabsf(v) <= max_dist && finite_f(len2) && len2 >= min_grad2;

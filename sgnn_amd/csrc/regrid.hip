@@ -15,7 +15,7 @@
 // bound on the fp32 error of the map (RgMap::pad, formed on the host), misses the source grid on some axis, rules
 // Q.3 - Q.6 fix every voxel of the block as unseen: store mode writes that, fold mode returns before any load.
 // No LDS, no atomics, plain vector loads and stores; the colour record moves as one 8-byte access.  The volume's four
-// pointers, the affine row and the fold of rule Q.8 are those of tsdf.h: merge folds exactly as points.hip does.
+// pointers and the fold of rule Q.8 are those of tsdf.h, the affine row geom.h's: merge folds exactly as points.hip does.
 //
 // Built with -ffp-contract=off (Makefile): every product and sum below is rounded on its own.
 #include <math.h>

@@ -23,7 +23,7 @@
 #include <math.h>
 #include <type_traits>
 #include "common.h"
-#include "tsdf.h"   // the affine row of transform()
+#include "geom.h"   // the affine row of transform() and the pinhole of snap()
 
 namespace {
 
@@ -88,8 +88,7 @@ __device__ __forceinline__ Col<true> clip_color(const Vec3 &a, const Vec3 &b, fl
 
 // rule 4: project and snap to 1/256 pixel; false when the vertex cannot be snapped
 __device__ __forceinline__ bool snap(const Vec3 &p, const float *intr, int64_t &X, int64_t &Y) {
-  const float u = __fdiv_rn(p.x * intr[0], p.z) + intr[2];
-  const float v = __fdiv_rn(p.y * intr[1], p.z) + intr[3];
+  const float u = geom_project(intr, 0, p.x, p.z), v = geom_project(intr, 1, p.y, p.z);
   const float sx = roundf(u * 256.0f), sy = roundf(v * 256.0f);   // half away from zero
   if (!(fabsf(sx) <= SNAP_LIMIT && fabsf(sy) <= SNAP_LIMIT)) return false;   // NaN and inf fail
   X = (int64_t)sx;

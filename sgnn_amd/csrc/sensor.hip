@@ -19,14 +19,13 @@
 // Built with -ffp-contract=off (Makefile): every product and sum is rounded on its own.
 #include <math.h>
 #include "common.h"
+#include "geom.h"   // finite_f and the pinhole of rule V.6
 
 namespace {
 
 constexpr int ROWS = 4;                        // rows (waves) per block of k_sensor_shadow
 constexpr float C8 = 1.86881243e-05f;          // 1 / sqrt(8 (65536^2 - 1) / 12): eight 16-bit fields (rule V.2)
 constexpr float C4 = 0.00676587503f;           // 1 / sqrt(4 (256^2 - 1) / 12): four 8-bit fields
-
-__device__ __forceinline__ bool finite_s(float v) { return fabsf(v) < INFINITY; }
 
 // round half away from zero, exact: the integer part, stepped by one when the fraction (exact in fp32) reaches 1/2
 __device__ __forceinline__ float round_away(float v) {
@@ -53,7 +52,7 @@ __global__ __launch_bounds__(ROWS * 64) void k_sensor_shadow(const float *__rest
     const int p = c * 64 + lane, x = flip ? w - 1 - p : p;
     const bool in = p < w;
     const float z = in ? d[x] : -INFINITY;
-    const bool valid = on && finite_s(z) && z > 0.f;
+    const bool valid = on && finite_f(z) && z > 0.f;
     const float u = (float)x - __fdiv_rn(fb, z);
     const float key = valid ? (flip ? -u : u) : INFINITY;
     float run = key;                                             // -> min of the keys of lanes >= this one
@@ -118,11 +117,11 @@ __global__ __launch_bounds__(256) void k_sensor_degrade(const float *__restrict_
     const float *p = depth + frame0 + (int64_t)sy * w + sx;
     // V.4
     const float z = p[0];
-    if (!finite_s(z) || z < M.min_depth || z > M.max_depth) break;
+    if (!finite_f(z) || z < M.min_depth || z > M.max_depth) break;
     // V.5
     const bool stereo = M.baseline != 0.f;
     if (stereo && mask[frame0 + (int64_t)sy * w + sx]) break;
-    const float fx = intr[4 * fi + 0], fy = intr[4 * fi + 1], cx = intr[4 * fi + 2], cy = intr[4 * fi + 3];
+    const float K[4] = {intr[4 * fi + 0], intr[4 * fi + 1], intr[4 * fi + 2], intr[4 * fi + 3]};   // fx, fy, cx, cy
     const bool noise = M.a0 != 0.f || M.a1 != 0.f;
     const uint64_t r3 = sgnn_hash64(at + 3u);
     // V.6
@@ -132,12 +131,12 @@ __global__ __launch_bounds__(256) void k_sensor_degrade(const float *__restrict_
       float c2 = 0.f;
       if (!edge) {
         const float dl = p[-1], dr = p[1], du = p[-w], dd = p[w];
-        edge = !(finite_s(dl) && finite_s(dr) && finite_s(du) && finite_s(dd));
+        edge = !(finite_f(dl) && finite_f(dr) && finite_f(du) && finite_f(dd));
         if (!edge) {
-          const float xl = __fdiv_rn((float)(sx - 1) - cx, fx), xc = __fdiv_rn((float)sx - cx, fx);
-          const float xr = __fdiv_rn((float)(sx + 1) - cx, fx);
-          const float yu = __fdiv_rn((float)(sy - 1) - cy, fy), yc = __fdiv_rn((float)sy - cy, fy);
-          const float yd = __fdiv_rn((float)(sy + 1) - cy, fy);
+          const float xl = geom_unproject(K, 0, (float)(sx - 1)), xc = geom_unproject(K, 0, (float)sx);
+          const float xr = geom_unproject(K, 0, (float)(sx + 1));
+          const float yu = geom_unproject(K, 1, (float)(sy - 1)), yc = geom_unproject(K, 1, (float)sy);
+          const float yd = geom_unproject(K, 1, (float)(sy + 1));
           // a = p(x+1, y) - p(x-1, y), b = p(x, y+1) - p(x, y-1), n = a x b, v = p(x, y)
           const float ax = xr * dr - xl * dl, ay = yc * dr - yc * dl, az = dr - dl;
           const float bx_ = xc * dd - xc * du, by_ = yd * dd - yu * du, bz = dd - du;
@@ -172,7 +171,7 @@ __global__ __launch_bounds__(256) void k_sensor_degrade(const float *__restrict_
     // V.9
     float z2 = z1;
     if (stereo && M.disparity_quantum != 0.f) {
-      const float B = fx * fabsf(M.baseline);
+      const float B = K[0] * fabsf(M.baseline);
       const float dq = round_away(__fdiv_rn(__fdiv_rn(B, z1), M.disparity_quantum)) * M.disparity_quantum;
       z2 = __fdiv_rn(B, dq);
       if (!(dq > 0.f && z2 > 0.f && z2 < INFINITY)) break;

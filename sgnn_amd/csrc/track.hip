@@ -24,7 +24,7 @@
 #include <math.h>
 #include "common.h"
 #include "gn_system.h"
-#include "tsdf.h"
+#include "geom.h"
 
 namespace {
 
@@ -60,32 +60,25 @@ __global__ __launch_bounds__(BLOCK) void k_track_normals(const float *__restrict
   const int idx = (int)blockIdx.x * BLOCK + (int)threadIdx.x;
   if (idx >= total) return;
   const int i = idx % w, t = idx / w, j = t % h, f = t / h;
-  float nx = NAN, ny = NAN, nz = NAN;
+  float n[3] = {NAN, NAN, NAN};
   if (i >= 1 && i + 1 < w && j >= 1 && j + 1 < h) {
     const float *p = depth + idx;
     const float dc = p[0], dl = p[-1], dr = p[1], du = p[-w], dd = p[w];
     if (finite_f(dc) && finite_f(dl) && finite_f(dr) && finite_f(du) && finite_f(dd) && fabsf(dl - dc) <= delta &&
         fabsf(dr - dc) <= delta && fabsf(du - dc) <= delta && fabsf(dd - dc) <= delta) {
-      const float fx = intr[4 * f + 0], fy = intr[4 * f + 1], cx = intr[4 * f + 2], cy = intr[4 * f + 3];
-      const float xl = __fdiv_rn((float)(i - 1) - cx, fx), xc = __fdiv_rn((float)i - cx, fx);
-      const float xr = __fdiv_rn((float)(i + 1) - cx, fx);
-      const float yu = __fdiv_rn((float)(j - 1) - cy, fy), yc = __fdiv_rn((float)j - cy, fy);
-      const float yd = __fdiv_rn((float)(j + 1) - cy, fy);
+      const float *K = intr + 4 * f;                // fx, fy, cx, cy
+      const float xl = geom_unproject(K, 0, (float)(i - 1)), xc = geom_unproject(K, 0, (float)i);
+      const float xr = geom_unproject(K, 0, (float)(i + 1));
+      const float yu = geom_unproject(K, 1, (float)(j - 1)), yc = geom_unproject(K, 1, (float)j);
+      const float yd = geom_unproject(K, 1, (float)(j + 1));
       // a = p(i+1, j) - p(i-1, j), b = p(i, j+1) - p(i, j-1)
       const float ax = xr * dr - xl * dl, ay = yc * dr - yc * dl, az = dr - dl;
       const float bx = xc * dd - xc * du, by = yd * dd - yu * du, bz = dd - du;
-      const float qx = by * az - bz * ay, qy = bz * ax - bx * az, qz = bx * ay - by * ax;   // b x a
-      const float len = (float)sqrt((double)((qx * qx + qy * qy) + qz * qz));              // correctly rounded
-      if (len > 0.f && len < INFINITY) {
-        nx = __fdiv_rn(qx, len);
-        ny = __fdiv_rn(qy, len);
-        nz = __fdiv_rn(qz, len);
-      }
+      geom_unit(by * az - bz * ay, bz * ax - bx * az, bx * ay - by * ax, n);   // b x a
     }
   }
-  normal[(int64_t)idx * 3 + 0] = nx;
-  normal[(int64_t)idx * 3 + 1] = ny;
-  normal[(int64_t)idx * 3 + 2] = nz;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) normal[(int64_t)idx * 3 + c] = n[c];
 }
 
 // Rules 2-4 for one live pixel: what "passes the geometric gates" means, for both system kernels.
@@ -102,17 +95,16 @@ __device__ __forceinline__ bool track_associate(const sgnn_track_pair &P, bool p
                                                 int j, const float *__restrict__ md, const float *__restrict__ mn,
                                                 int hm, int wm, float max_dist2, float cos_min, TrackHit &H) {
   const float *T = P.t;
-  const float fxl = P.intr_live[0], fyl = P.intr_live[1], cxl = P.intr_live[2], cyl = P.intr_live[3];
-  const float fxm = P.intr_model[0], fym = P.intr_model[1], cxm = P.intr_model[2], cym = P.intr_model[3];
+  const float Kl[4] = {P.intr_live[0], P.intr_live[1], P.intr_live[2], P.intr_live[3]};       // fx, fy, cx, cy
+  const float Km[4] = {P.intr_model[0], P.intr_model[1], P.intr_model[2], P.intr_model[3]};
   // rule 2
   bool ok = pose_ok && finite_f(d) && d > 0.f;
-  const float lx = __fdiv_rn((float)i - cxl, fxl) * d, ly = __fdiv_rn((float)j - cyl, fyl) * d;
+  const float lx = geom_unproject(Kl, 0, (float)i) * d, ly = geom_unproject(Kl, 1, (float)j) * d;
   tsdf_affine(T, lx, ly, d, H.q);
   const float qx = H.q[0], qy = H.q[1], qz = H.q[2];
   // rule 3
   ok = ok && qz > 0.f;
-  H.x = __fdiv_rn(qx * fxm, qz) + cxm;
-  H.y = __fdiv_rn(qy * fym, qz) + cym;
+  H.x = geom_project(Km, 0, qx, qz), H.y = geom_project(Km, 1, qy, qz);
   const float u = roundf(H.x), v = roundf(H.y);
   ok = ok && u >= 0.f && u < (float)wm && v >= 0.f && v < (float)hm;     // a NaN fails
   const int mi = ok ? (int)v * wm + (int)u : 0;
@@ -121,16 +113,14 @@ __device__ __forceinline__ bool track_associate(const sgnn_track_pair &P, bool p
   const float nx = mn[(int64_t)mi * 3 + 0], ny = mn[(int64_t)mi * 3 + 1], nz = mn[(int64_t)mi * 3 + 2];
   H.n[0] = nx, H.n[1] = ny, H.n[2] = nz;
   ok = ok && finite_f(dm) && dm > 0.f && finite_f(nx) && finite_f(ny) && finite_f(nz);
-  const float mx = __fdiv_rn(u - cxm, fxm) * dm, my = __fdiv_rn(v - cym, fym) * dm;
+  const float mx = geom_unproject(Km, 0, u) * dm, my = geom_unproject(Km, 1, v) * dm;
   // rule 4
   const float ex = qx - mx, ey = qy - my, ez = qz - dm;
   H.e[0] = ex, H.e[1] = ey, H.e[2] = ez;
   ok = ok && (ex * ex + ey * ey) + ez * ez <= max_dist2;
   if (ANGLE) {
-    const float l0 = l[0], l1 = l[1], l2 = l[2];
-    const float rx = (T[0] * l0 + T[1] * l1) + T[2] * l2;
-    const float ry = (T[4] * l0 + T[5] * l1) + T[6] * l2;
-    const float rz = (T[8] * l0 + T[9] * l1) + T[10] * l2;
+    const float rx = geom_linear_row(T, 0, l[0], l[1], l[2]), ry = geom_linear_row(T, 1, l[0], l[1], l[2]);
+    const float rz = geom_linear_row(T, 2, l[0], l[1], l[2]);
     ok = ok && (rx * nx + ry * ny) + rz * nz >= cos_min;                 // a NaN live normal fails
   }
   return ok;

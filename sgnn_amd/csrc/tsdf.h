@@ -1,35 +1,10 @@
 // The per-voxel state of a TSDF volume (sdf, weight, free counter, 8.8 colour record) and the rules every entrance to a
 // volume shares: fusion.hip (depth frames), points.hip (point clouds) and regrid.hip (resample / merge).  INTEGRATION.md
 // sections D, M, P and Q are the contract; this header is the one place their common expressions are written, so the
-// restatements of the tests hold all three files to the same bits.  render.hip and voxelize.hip take the affine row only.
+// restatements of the tests hold all three files to the same bits.  The affine maps and finite_f live in geom.h.
 // No kernels here.  Every includer is built with -ffp-contract=off: each product and sum below is rounded on its own.
 #pragma once
-#include <math.h>
-#include "common.h"
-
-__device__ __forceinline__ bool finite_f(float v) { return fabsf(v) < INFINITY; }   // false for a NaN
-
-// ---- affine maps: rows 0..2 of a 4x4, row-major --------------------------------------------------------------------
-struct TsdfAffine { float m[12]; };
-
-// ((m0 x + m1 y) + m2 z) + m3 of row r: the order of fusion._affine
-__device__ __forceinline__ float tsdf_affine_row(const float *m, int r, float x, float y, float z) {
-  return ((m[4 * r] * x + m[4 * r + 1] * y) + m[4 * r + 2] * z) + m[4 * r + 3];
-}
-
-__device__ __forceinline__ void tsdf_affine(const float *m, float x, float y, float z, float (&out)[3]) {
-#pragma unroll
-  for (int r = 0; r < 3; ++r) out[r] = tsdf_affine_row(m, r, x, y, z);
-}
-
-// 0: an entry is not finite
-static inline int tsdf_affine_arg(const float *host12, TsdfAffine &a) {
-  for (int c = 0; c < 12; ++c) {
-    if (!isfinite(host12[c])) return 0;
-    a.m[c] = host12[c];
-  }
-  return 1;
-}
+#include "geom.h"
 
 // ---- the oriented box outside of which a volume is never updated (voxel coordinates) ----------------------------------
 struct TsdfObb {

@@ -19,7 +19,7 @@
 // Built with -ffp-contract=off (Makefile): every product and sum is rounded on its own.
 #include <math.h>
 #include "common.h"
-#include "tsdf.h"
+#include "geom.h"
 
 namespace {
 
@@ -70,12 +70,8 @@ __device__ __forceinline__ void up_walk(const UpVolume &V, F f) {
     UpVoxel s;
     s.x = x, s.y = y, s.z = z, s.v = v;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) s.m[k] = (M[k] * gx + M[4 + k] * gy) + M[8 + k] * gz;
-    const float len2 = (s.m[0] * s.m[0] + s.m[1] * s.m[1]) + s.m[2] * s.m[2];
-    if (!(len2 > 0.f && len2 < INFINITY)) continue;
-    const float len = (float)sqrt((double)len2);   // correctly rounded (the fp32 root is not)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) s.n[k] = __fdiv_rn(s.m[k], len);
+    for (int k = 0; k < 3; ++k) s.m[k] = geom_linear_col(M, k, gx, gy, gz);
+    if (!geom_unit<true>(s.m[0], s.m[1], s.m[2], s.n)) continue;
     f(s);
   }
 }

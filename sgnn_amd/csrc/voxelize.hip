@@ -22,7 +22,7 @@
 #include "box_lists.h"  // the brick walk of k_vox_bricks, shared with meshdist.hip
 #include "first_table.h"
 #include "tri_dist.h"
-#include "tsdf.h"       // the affine row of k_vox_grid_coords
+#include "geom.h"       // the affine row of k_vox_grid_coords
 
 namespace {
 

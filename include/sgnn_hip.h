@@ -1052,6 +1052,29 @@ int sgnn_sensor_degrade(const float *depth, const uint8_t *mask, int nframes, in
                         sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Arbitrary rays against a triangle mesh (sgnn_amd.raytrace; rules in INTEGRATION.md section W): the closest hit of
+ * every ray, or whether anything lies on a segment.  The mesh is the index of the mesh-distance block above: records
+ * from sgnn_meshdist_pack, offsets / refs from sgnn_meshdist_count / fill run on boxes grown by `guard` on every side
+ * (rule W.4), over the grid lo (3 floats), pitch cell > 0, nx, ny, nz cells (nx*ny*nz < 2^31), all finite, guard >= 0.
+ * origins, dirs (nrays, 3) f32; a ray is origin + t dir, dir is used as given (not normalised).  A face is hit iff the
+ * test of rule W.1 passes with t_min < t < t_max (t_min finite); cull_back (0 or 1) = 1 keeps faces with det > 0 only.
+ * counters: NULL, or device int64[2] that the call adds to: cells visited, (ray, face) pairs tested.
+ *   sgnn_raytrace_closest  -> t (nrays) f32, face (nrays) i32, uv (nrays, 2) f32 of the smallest t over all usable
+ *                             faces, the lowest face index among equal t; a miss is +inf, -1, (0, 0).  t_min < t_max.
+ *   sgnn_raytrace_occluded -> hit (nrays) u8: 1 iff some usable face is hit within (t_min, t_max[ray]); t_max (nrays)
+ *                             f32 on the device, a ray whose t_max is not above t_min is a miss.
+ * A ray with a non-finite component or a zero direction is a miss.
+ * ------------------------------------------------------------------------- */
+int sgnn_raytrace_closest(const float *origins, const float *dirs, int64_t nrays, float t_min, float t_max,
+                          const float *records, const int32_t *offsets, const int32_t *refs, float lox, float loy,
+                          float loz, float cell, int nx, int ny, int nz, float guard, int cull_back, float *t,
+                          int32_t *face, float *uv, int64_t *counters, sgnn_stream_t stream);
+int sgnn_raytrace_occluded(const float *origins, const float *dirs, int64_t nrays, float t_min, const float *t_max,
+                           const float *records, const int32_t *offsets, const int32_t *refs, float lox, float loy,
+                           float loz, float cell, int nx, int ny, int nz, float guard, int cull_back, uint8_t *hit,
+                           int64_t *counters, sgnn_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Connected components of volumes and meshes (sgnn_amd.components; rules in INTEGRATION.md section J): lock-free
  * union-find on parent[] (i32, one slot per voxel or vertex; -1 = background / unreferenced).  Larger indices are
  * hooked onto smaller ones, so parent[i] <= i at all times and the root of a finished component is its smallest index.

@@ -12,6 +12,7 @@ Package contents (only what the hot path of SURVEY.md §8 needs):
   register.py  point sets and volumes registered against a TSDF volume: transforms for regrid.merge (section R)
   upright.py   the gravity-aligned room frame of a scan volume: the transform for regrid.grid_for (section S)
   sensor.py    a depth sensor simulated on rendered frames: noise, disparity steps, shadow, ragged edges (section V)
+  raytrace.py  arbitrary rays against a triangle mesh: closest hits, scanner sweeps for points, visibility (section W)
 """
 __version__ = '0.1.0'
 
@@ -22,7 +23,7 @@ def __getattr__(name):
     if name == 'bf16_inference':
         from .scn.program import bf16_inference
         return bf16_inference
-    if name in ('track', 'register', 'upright', 'sensor'):   # sgnn_amd.track / .register / .upright / .sensor without an import statement of their own, as lazily as the above
+    if name in ('track', 'register', 'upright', 'sensor', 'raytrace'):   # sgnn_amd.track / .register / .upright / .sensor / .raytrace without an import statement of their own, as lazily as the above
         import importlib
         return importlib.import_module('.' + name, __name__)
     raise AttributeError(name)

@@ -174,6 +174,10 @@ PROTOTYPES = {
                                      c_vp, c_vp]),
     'sgnn_sensor_shadow': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_f32, c_vp, c_vp]),
     'sgnn_sensor_degrade': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_u64, c_vp, c_vp]),
+    'sgnn_raytrace_closest': (c_i32, [c_vp, c_vp, c_i64, c_f32, c_f32, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_i32,
+                                      c_i32, c_i32, c_f32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'sgnn_raytrace_occluded': (c_i32, [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_i32,
+                                       c_i32, c_i32, c_f32, c_i32, c_vp, c_vp, c_vp]),
     'sgnn_cc_volume_link': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'sgnn_cc_mesh_link': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
     'sgnn_cc_flatten': (c_i32, [c_vp, c_i64, c_vp, c_vp]),

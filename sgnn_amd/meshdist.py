@@ -66,10 +66,11 @@ class TriangleIndex:
 
     cell: grid pitch in the units of verts; None takes default_cell.  Raises ValueError for a malformed mesh, a face
     index out of range, a mesh without a usable face, and a pitch so small that the grid or its (face, cell)
-    reference list would not fit."""
+    reference list would not fit.  guard: every face is listed in the cells of its box grown by guard * cell on every
+    side (raytrace.Scene, section W rule 4); 0 lists it in the cells its own box touches, all that `distance` needs."""
 
-    def __init__(self, verts, faces, cell=None):
-        self._build(_Packed(verts, faces), cell)
+    def __init__(self, verts, faces, cell=None, guard=0.0):
+        self._build(_Packed(verts, faces), cell, guard)
 
     @classmethod
     def _from_packed(cls, packed, cell=None):
@@ -77,7 +78,7 @@ class TriangleIndex:
         index._build(packed, cell)
         return index
 
-    def _build(self, p, cell):
+    def _build(self, p, cell, guard=0.0):
         self.packed, self.device = p, p.device
         self.lo = p.boxes[:, :3].amin(0).cpu().numpy().astype(F32)          # ignored faces hold (+inf, -inf)
         self.hi = p.boxes[:, 3:].amax(0).cpu().numpy().astype(F32)
@@ -94,8 +95,14 @@ class TriangleIndex:
         self.dims = tuple(int(s) for s in span)                              # nx, ny, nz
         ncell = self.dims[0] * self.dims[1] * self.dims[2]
         grid = (float(self.lo[0]), float(self.lo[1]), float(self.lo[2]), float(self.cell)) + self.dims
+        self.guard = F32(F32(guard) * self.cell)
+        if not (np.isfinite(self.guard) and self.guard >= 0):
+            raise ValueError('guard must be finite and not negative, got %r' % (guard,))
+        boxes = p.boxes
+        if self.guard > 0:                                                   # ignored faces keep (+inf, -inf)
+            boxes = torch.cat([boxes[:, :3] - float(self.guard), boxes[:, 3:] + float(self.guard)], 1).contiguous()
         self.offsets, self.refs, self.n_refs = binned_lists(
-            'sgnn_meshdist_count', 'sgnn_meshdist_fill', (p.boxes.data_ptr(), p.ntri) + grid, ncell, self.device,
+            'sgnn_meshdist_count', 'sgnn_meshdist_fill', (boxes.data_ptr(), p.ntri) + grid, ncell, self.device,
             '%%d (face, cell) references do not fit 31 bits at cell = %g: choose a larger cell' % self.cell)
 
     def _keys(self, pts):

@@ -974,6 +974,25 @@ int sgnn_register_system(const float *points, int npoints, const float *sdf, int
                          double *out, float *residual, int32_t *cell, void *ws, int64_t ws_bytes,
                          sgnn_stream_t stream);
 
+/* Candidate transforms scored against an integer distance field (register.search; rules in INTEGRATION.md section X).
+ * One candidate of sgnn_register_score (48 bytes; the record table is a device array of these): */
+typedef struct sgnn_register_pose {
+  float m[12]; /* rows 0..2 of world2grid . T: source world (x,y,z,1) -> voxel coordinates of the field, formed in fp64
+                  and rounded to fp32 by the caller; NaN = non-finite record, every point outside */
+} sgnn_register_pose;
+#define SGNN_REGISTER_SCORE_MAX_POSES (1 << 24) /* records of one sgnn_register_score call */
+/* out (nposes, 3) i64, written in full by the call: per record the cost, the inliers and the points outside.  points
+ * (npoints, 3) f32 in the source world, shared by all records; dist2 (dz, dy, dx) i32: squared distances in voxels, -1 =
+ * nothing within reach (sgnn_edt_axis' dist2).  A point goes to voxel n = floor(g + 0.5f) per axis of g = m . p; it is
+ * outside where g is not finite or 0 <= n <= d - 1 fails, tested in float.  An outside point costs cap2; one inside
+ * costs cap2 where dist2[n] < 0, else min(dist2[n], cap2), and is an inlier where 0 <= dist2[n] <= inlier2.  The sums
+ * are exact integers: no bit depends on nposes, on the launch or on the order of the additions.
+ * npoints < 2^31 - 65536; nposes <= SGNN_REGISTER_SCORE_MAX_POSES; dx, dy, dz >= 1 and dx * dy * dz < 2^31; cap2 > 0;
+ * inlier2 >= 0.  npoints == 0 writes zeros; nposes == 0 launches nothing and writes nothing. */
+int sgnn_register_score(const float *points, int npoints, const int32_t *dist2, int dx, int dy, int dz,
+                        const sgnn_register_pose *poses, int nposes, int cap2, int inlier2, int64_t *out,
+                        sgnn_stream_t stream);
+
 /* ---------------------------------------------------------------------------
  * The gravity-aligned room frame of a volume (sgnn_amd.upright; rules in INTEGRATION.md section S): votes of the
  * surface normals of a TSDF volume.  A surface voxel is an interior voxel whose sdf and six axis neighbours are finite

@@ -168,6 +168,7 @@ PROTOTYPES = {
                                         c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     'sgnn_register_system': (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_f32, c_f32, c_f32, c_vp, c_vp,
                                      c_vp, c_vp, c_i64, c_vp]),
+    'sgnn_register_score': (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'sgnn_upright_histogram': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_f32, c_f32, c_i32, c_vp, c_vp]),
     'sgnn_upright_sums': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_f32, c_f32, c_vp, c_i32, c_vp, c_vp]),
     'sgnn_upright_heights': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_f32, c_f32, c_vp, c_f32, c_f32, c_f32, c_i32,

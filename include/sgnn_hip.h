@@ -149,6 +149,14 @@ typedef struct sgnn_tune {
    * inside the apply kernels, as bn_fuse_ok decides; 0 = always the separate finalize kernels.  The two add the fp64
    * partials in different fixed orders (fp64 round-off before the fp32 results).  Default 1. */
   int64_t bn_fuse;
+  /* sgnn_prog_forward / _backward (with prog_fusion and bn_fuse): a training-layout BatchNormReLU whose only reader is the
+   * next op, a <= 16-channel convolution on a small level (the 16-row forward kernel and the one-offset weight gradient run there) and whose
+   * statistics partials come from a convolution epilogue is not run as a pass of its own: the convolution sums the partial
+   * table itself (in the order of the apply kernel), applies the layer to the rows it gathers, and its first workgroup stores
+   * save_mean / save_invstd and updates the running statistics; the weight gradient applies the layer the same way.  The
+   * layer's output buffer is never written (it keeps its slot: the gradient arena shares the layout and holds the layer's dy
+   * there).  Outputs, statistics and gradients bit-identical.  0 = the layer runs as a pass.  Default 1. */
+  int64_t prog_bn_fold_small;
 } sgnn_tune;
 int64_t sgnn_tune_set(const char *name, int64_t value);
 int64_t sgnn_tune_get(const char *name);

@@ -13,14 +13,13 @@
 // Thread mapping keeps a thread on a fixed channel group: blockDim = RPB rows x CQ column
 // groups, CQ = C/VEC, so per-channel constants live in registers.
 #include "common.h"
+#include "bn_fuse.h"
 
 #define BN_MAX_BLOCKS 2048
 #define BN_FLUSH 2
 #ifndef BN_U
 #define BN_U 2            // row groups a thread of the apply passes loads before it uses the first one (4 / 8: measured, no gain)
 #endif
-#define BN_FUSE_BLOCKS 4096
-#define BN_FUSE_MAXC 64
 
 struct BnGeom {
   int vec;   // 4 or 1 floats per thread-column
@@ -280,90 +279,8 @@ __global__ __launch_bounds__(256) void k_bn_eval_stats(const float *__restrict__
   }
 }
 
-// Small levels (few block partials, C <= BN_FUSE_MAXC): the apply kernels finalise the statistics themselves — every
-// workgroup sums the short partial table in the same fixed order into LDS, workgroup 0 also stores the results the
-// later passes / the caller need — and the separate finalize launch disappears.
-
-struct BnFuse {
-  const double *partial;   // NULL: statistics come from the mean/invstd (or coef) arrays
-  int nblk;
-  float eps, momentum;
-  float *running_mean, *running_var, *save_mean, *save_invstd;   // forward
-  float *dgamma, *dbeta;                                          // backward
-};
-
-// Per-channel totals of the block partials, computed by the whole workgroup: 256/c threads share a channel (strided
-// partial sums), their pieces are added in thread order — a fixed order, identical in every workgroup.
-// tot[0..c) = sum_a, tot[c..2c) = sum_b;  scratch: 512 doubles.  Contains two barriers.
-// Round 6: what this costs is the NUMBER of dependent load rounds, ~0.75 us each (the table was written by the producing
-// kernel's workgroups on all eight XCDs: every first touch misses this XCD's L2) — 6 rounds for the 684 16-row partials of a
-// 11 k-row level with one 8-byte load per value and 8 blocks in flight (k_bn_apply 7.4 us there against 4.5 us on a 60 k-row
-// level with 236 partials).  Even channel counts read two channels per 16-byte load and keep 32 loads in flight: the same
-// table in 2 rounds.  The kernels that call this are the FUSE instantiations (small levels only), so the 64 + 64 registers
-// cost the streaming instantiations nothing.  Any fixed order is a valid order: deterministic per (nblk, c).
-#ifndef BN_TOTALS_WIDE
-#define BN_TOTALS_WIDE 1     // 0: the one-value-per-load form everywhere (scripts/build_variant.sh A/B builds)
-#endif
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void bn_fuse_totals(const BnFuse &f, int c, double *scratch, double *tot) {
-  const int tid = threadIdx.x;
-  const int tpc = 256 / c;                       // >= 4 for c <= BN_FUSE_MAXC
-  if (BN_TOTALS_WIDE && (c & 1) == 0 && (((uintptr_t)f.partial) & 15) == 0) {
-    // thread = (part, which, channel pair): sums `which` (0: sum_a, 1: sum_b) of channels 2 p, 2 p + 1 over blocks part, part + tpc, ...
-    const int hp = c >> 1;
-    const int p2 = tid % hp, which = (tid / hp) & 1, part = tid / c;
-    f64x2 acc = {0.0, 0.0};
-    if (part < tpc) {
-      constexpr int U = 32;
-      for (int blk = part; blk < f.nblk; blk += U * tpc) {
-        f64x2 v[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int bi = blk + u * tpc;
-          v[u] = bi < f.nblk ? *reinterpret_cast<const f64x2 *>(f.partial + ((size_t)bi * 2 + which) * c + 2 * p2) : f64x2{0.0, 0.0};
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) acc += v[u];
-      }
-      scratch[which * 256 + part * c + 2 * p2] = acc[0];
-      scratch[which * 256 + part * c + 2 * p2 + 1] = acc[1];
-    }
-  } else {
-    const int ch = tid % c, part = tid / c;
-    double a = 0.0, b = 0.0;
-    if (part < tpc) {
-      // eight independent loads in flight per thread; the additions keep their order, missing entries add an exact 0.0
-      for (int blk = part; blk < f.nblk; blk += 8 * tpc) {
-        double va[8], vb[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int bi = blk + u * tpc;
-          const bool ok = bi < f.nblk;
-          va[u] = ok ? f.partial[((size_t)bi * 2 + 0) * c + ch] : 0.0;
-          vb[u] = ok ? f.partial[((size_t)bi * 2 + 1) * c + ch] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          a += va[u];
-          b += vb[u];
-        }
-      }
-      scratch[part * c + ch] = a;
-      scratch[256 + part * c + ch] = b;
-    }
-  }
-  __syncthreads();
-  if (tid < c) {
-    double s1 = 0.0, s2 = 0.0;
-    for (int p = 0; p < tpc; ++p) {
-      s1 += scratch[p * c + tid];
-      s2 += scratch[256 + p * c + tid];
-    }
-    tot[tid] = s1;
-    tot[c + tid] = s2;
-  }
-  __syncthreads();
-}
+// (BnFuse, bn_fuse_totals and bn_fuse_ok live in bn_fuse.h: the folded small-level convolution of conv.hip sums the same
+// tables in the same order)
 
 // Thread mapping of the apply passes = the one of the statistics pass: a thread owns one column group (VEC channels, its
 // constants live in registers) and walks rows row0 + i*step, BN_U rows in flight; ldx / ldy = row strides (floats).
@@ -541,16 +458,6 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(const float *__restrict__ 
       store_vec<VEC>(dx + r * ld_dx + col * VEC, ov);
     }
   }
-}
-
-// Finalising inside the apply kernels makes EVERY apply workgroup re-sum the partial table (L2-resident): worth it as
-// long as that re-read stays small next to a separate launch (~5 us of GPU time + ~3 us of host time per finalize, ~70
-// of them per training step).  Budget: 48 MB of partial reads per apply launch.
-// (A finalise kernel made of ONE 1024-thread workgroup that reads the partial table in coalesced rows was measured against
-//  the c single-channel workgroups of k_bn_finalize_fwd / _bwd: +3.8 us per launch inside the step, 6.64 vs 6.51 ms per step
-//  — one CU cannot pull a 366 KB table as fast as 16 can; dropped.)
-static bool bn_fuse_ok(int64_t nblk, int c, int apply_grid) {
-  return c <= BN_FUSE_MAXC && nblk <= BN_FUSE_BLOCKS && nblk * (int64_t)apply_grid * 2 * c * (int64_t)sizeof(double) <= (48ll << 20);
 }
 
 static int bn_apply_grid(int64_t n, const BnGeom &g) {

@@ -48,7 +48,10 @@ struct ConvEpi {
 int sgnn_conv_fwd_impl(const float *x, int64_t n_in, int cin, const float *w, int K, const int32_t *table, int64_t ld,
                        int64_t n_out, int cout, float *y, int flags, int in_shift, const int32_t *kmap,
                        const int32_t *kadd, int in_mul, int groups, int table_rows, const ConvEpi *epi,
-                       sgnn_stream_t stream);
+                       sgnn_stream_t stream, const struct ConvPre *pre = nullptr);
+// pre (here and in sgnn_conv_bwd_weight_impl): a BatchNormReLU folded into the gathers of a small-level convolution
+// (bn_fuse.h; prog.hip plans it where sgnn_conv_fold_small_ok holds)
+bool sgnn_conv_fold_small_ok(int cin, int cout, int K, int64_t n_out);
 int64_t sgnn_conv_grid_blocks(int64_t n_out, int cin, int cout, int K);
 // BatchNorm backward whose incoming gradient is the data gradient of a per-site linear head that nobody else reads (the
 // surface head, model.py:433-447): dy[r][ch] = sum_o g[r*ldg + o] * w[o][ch] is formed in the two BatchNorm passes instead of
@@ -114,7 +117,8 @@ int sgnn_concat3_rows_bwd_dn(const float *ddst, int ca, const int32_t *ia, int c
 int sgnn_conv_bwd_weight_impl(const float *x, int64_t n_in, int cin, int64_t ldx, const float *dy, int cout, int64_t ld_dy,
                               const int32_t *table, int64_t ld, int K, int64_t n_out, float *dw, int in_shift,
                               const int32_t *kmap, const int32_t *kadd, int in_mul, int groups, int table_rows, void *ws,
-                              int64_t ws_bytes, sgnn_stream_t stream, const int64_t *n_dev = nullptr);
+                              int64_t ws_bytes, sgnn_stream_t stream, const int64_t *n_dev = nullptr,
+                              const struct ConvPre *pre = nullptr);
 int sgnn_expand_maps(const int32_t **S, const int32_t **ST, const int32_t **PAR);
 // linear.hip: heads whose weight rows / biases are separate tensors
 int sgnn_linear_fwd_rows(const float *x, int64_t n, int cin, const float *const *w, const float *const *b, int cout,

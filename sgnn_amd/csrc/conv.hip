@@ -21,6 +21,7 @@
 #include "common.h"
 
 #include "conv_common.h"
+#include "bn_fuse.h"
 
 // below this many 256-row workgroups the latency-oriented small-level kernel runs (sgnn_tune.conv_small_rows, ~40 k rows)
 #define CONV_SMALL_GRID ((int64_t)((g_tune.conv_small_rows + CONV_ROWS_PER_BLOCK - 1) / CONV_ROWS_PER_BLOCK))
@@ -279,16 +280,36 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 // accumulators, and the four partial tiles are summed through LDS.  Same arithmetic per (row, offset); the summation
 // order over offsets differs from the big kernel (fp32 round-off only).  Plain rulebook walk only.
 // ---------------------------------------------------------------------------
-template <int CIN, int COUT>
+//
+// PRE (k_conv_small<CIN, COUT, ConvPre>, forward pass only): x holds the INPUT rows of a BatchNormReLU that nothing but this convolution
+// reads; the kernel applies that layer to every value it gathers and the layer's output is never stored.  Training: the
+// producer's statistics partials are summed here — the table loads are the first memory instructions of the kernel and are
+// consumed after the rule entries, the gathers and the weight fragments have been issued, so their two round trips run under
+// the rule -> gather chain — in the order of bn_fuse_totals, and mean / invstd follow by the expressions of k_bn_apply<.., true>:
+// the same bits.  Workgroup 0 stores save_mean / save_invstd and updates the running statistics, as workgroup 0 of the apply
+// kernel did.  Eval: mean / invstd from the running statistics by the expressions of k_bn_eval_stats.  Rows of missing rules
+// stay exact zeros (the activation of a zero row is not zero).
+// The folded layer is a trailing parameter PACK: empty for k_conv_small<CIN, COUT>, whose signature and code stay what they
+// were, one ConvPre for k_conv_small<CIN, COUT, ConvPre>.
+template <class T>
+__device__ __forceinline__ const T &conv_pack_first(const T &t) { return t; }
+
+template <int CIN, int COUT, class... PREARG>
 __global__ __launch_bounds__(256) void k_conv_small(const float *__restrict__ x, int64_t n_in,
                                                    const float *__restrict__ w, const int32_t *__restrict__ table,
                                                    int64_t ld, int K, int64_t n_out, float *y, int flags, int in_shift,
-                                                   ConvEpi epi) {
+                                                   ConvEpi epi, PREARG... prearg) {
+  constexpr bool PRE = sizeof...(PREARG) == 1;
+  static_assert(sizeof...(PREARG) <= 1, "at most one folded layer");
   using C = ConvCfg<CIN, COUT>;
   constexpr int V = C::V, CINP = C::CINP, NT = C::NT;
   constexpr int KW = 7;                       // offsets per wave (K <= 28)
   __shared__ float red[4][NT * 256];          // the four waves' partial 16 x (NT*16) tiles
   __shared__ double sred[4][2][NT * 16];
+  constexpr int PC = PRE ? CIN : 1;
+  __shared__ double pre_scratch[PRE ? 512 : 1], pre_tot[2 * PC];
+  __shared__ float pre_mean[PC], pre_inv[PC];
+  static_assert(!PRE || (CINP == CIN && (CIN & 1) == 0 && CIN <= 16), "folded BatchNorm: whole quarters, the wide table form");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 15, q = lane >> 4;
   const int64_t row0 = (int64_t)blockIdx.x * 16;
@@ -311,6 +332,27 @@ __global__ __launch_bounds__(256) void k_conv_small(const float *__restrict__ x,
   const __amdgpu_buffer_rsrc_t rs_y = make_rsrc(y, (uint32_t)(((n_out - 1) * epi.ldy + COUT) * 4));
   const uint32_t lane_off = (uint32_t)(row0 + r) * 4u;
   const uint32_t ld4 = (uint32_t)ld * 4u;
+
+  // PRE: the statistics first — nothing below depends on them until the gathered values are used
+  BnTotalsEarly<PC == 1 ? 2 : PC> pre_early;
+  float km[PRE ? V : 1], ki[PRE ? V : 1], kg[PRE ? V : 1], kb[PRE ? V : 1];
+  if constexpr (PRE) {
+    const ConvPre &pre = conv_pack_first(prearg...);
+    if (pre.fuse.partial) {
+      bn_totals_issue<CIN>(pre.fuse, pre_early);
+    } else {
+#pragma unroll
+      for (int s = 0; s < V; ++s) {
+        km[s] = pre.fuse.running_mean[q * V + s];
+        ki[s] = pre.fuse.running_var[q * V + s];
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < V; ++s) {
+      kg[s] = pre.gamma ? pre.gamma[q * V + s] : 1.f;
+      kb[s] = pre.beta ? pre.beta[q * V + s] : 0.f;
+    }
+  }
 
   // one round trip: the rule entries of all offsets of this wave (offsets past nk are clamped and ignored)
   int32_t id[KW];
@@ -420,6 +462,53 @@ __global__ __launch_bounds__(256) void k_conv_small(const float *__restrict__ x,
 #pragma unroll
       for (int s = 0; s < V; ++s)
         if (3 * V + s >= CIN) a[kk][s] = (q >= conv_first_pad_quarter<CIN, V>(s)) ? 0.f : a[kk][s];
+  }
+  if constexpr (PRE) {
+    const ConvPre &pre = conv_pack_first(prearg...);
+    if (pre.fuse.partial) {                      // uniform over the launch: every thread passes both barriers
+      const int64_t n_bn = sgnn_dyn_n(pre.n_bn, pre.n_bn_dev);
+      bn_totals_finish<CIN>(pre.fuse, pre_early, pre_scratch, pre_tot);
+      if (tid < CIN) {                           // (the thread that wrote pre_tot[tid], pre_tot[CIN + tid])
+        const BnFuse &fuse = pre.fuse;
+        const int ch = tid;
+        const double s1 = pre_tot[ch], s2 = pre_tot[CIN + ch];
+        const double mu = s1 / (double)n_bn;
+        double var = s2 / (double)n_bn - mu * mu;
+        if (var < 0.0) var = 0.0;
+        const float fm = (float)mu, fi = (float)(1.0 / sqrt(var + (double)fuse.eps));
+        pre_mean[ch] = fm;
+        pre_inv[ch] = fi;
+        if (blockIdx.x == 0) {
+          fuse.save_mean[ch] = fm;
+          fuse.save_invstd[ch] = fi;
+          if (fuse.running_mean) fuse.running_mean[ch] = fuse.momentum * fuse.running_mean[ch] + (1.f - fuse.momentum) * fm;
+          if (fuse.running_var) {
+            const double unb = var * ((double)n_bn / (double)(n_bn > 1 ? n_bn - 1 : 1));
+            fuse.running_var[ch] = fuse.momentum * fuse.running_var[ch] + (1.f - fuse.momentum) * (float)unb;
+          }
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int s = 0; s < V; ++s) {
+        km[s] = pre_mean[q * V + s];
+        ki[s] = pre_inv[q * V + s];
+      }
+    } else {
+#pragma unroll
+      for (int s = 0; s < V; ++s) ki[s] = 1.0f / sqrtf(ki[s] + pre.fuse.eps);
+      if (blockIdx.x == 0 && wave == 0 && r == 0) {
+#pragma unroll
+        for (int s = 0; s < V; ++s) {
+          pre.fuse.save_mean[q * V + s] = km[s];
+          pre.fuse.save_invstd[q * V + s] = ki[s];
+        }
+      }
+    }
+#pragma unroll
+    for (int kk = 0; kk < KW; ++kk)
+#pragma unroll
+      for (int s = 0; s < V; ++s) a[kk][s] = id[kk] < 0 ? 0.f : sgnn_bn_act(a[kk][s], km[s], ki[s], kg[s], kb[s], pre.leak);
   }
   f32x4 acc[2][NT];
 #pragma unroll
@@ -544,6 +633,23 @@ __global__ __launch_bounds__(256) void k_conv_fwd_generic(const float *__restric
   X(8, 1) X(12, 8) X(16, 12) X(16, 34) X(16, 30) X(16, 26) X(16, 48) X(32, 16) X(16, 32) X(4, 16) X(16, 4) \
   X(16, 24) X(24, 16) X(24, 32) X(32, 24) X(64, 32) X(32, 64) X(56, 28) X(28, 56) X(32, 32) X(28, 16) X(16, 28)
 
+// shapes whose small-level forward kernel and one-offset weight gradient exist with a folded BatchNormReLU in front of the
+// gathers (PRE): the <= 16-channel layers of the U-Net levels
+#define CONV_PRE_CASES(X) X(8, 8) X(8, 12) X(12, 12) X(12, 16) X(16, 16) X(4, 16)
+#define DW_FINE_ROWS 16384   // below: one offset per weight-gradient workgroup
+
+// a convolution of this shape over n_out output rows runs k_conv_small forward and k_conv_dw<.., 1> for its weight gradient
+// under the current switches: the two kernels that can apply a folded BatchNormReLU
+bool sgnn_conv_fold_small_ok(int cin, int cout, int K, int64_t n_out) {
+  const int64_t grid4 = (n_out + CONV_ROWS_PER_BLOCK - 1) / CONV_ROWS_PER_BLOCK;
+  if (!g_tune.conv_small || K > 28 || n_out <= 0 || grid4 >= CONV_SMALL_GRID || n_out >= DW_FINE_ROWS) return false;
+#define X(CI, CO) \
+  if (cin == CI && cout == CO) return true;
+  CONV_PRE_CASES(X)
+#undef X
+  return false;
+}
+
 // number of workgroups (= statistics partial blocks) a plain launch over n_out rows uses
 int64_t sgnn_conv_grid_blocks(int64_t n_out, int cin, int cout, int K) {
   const int64_t grid4 = (n_out + CONV_ROWS_PER_BLOCK - 1) / CONV_ROWS_PER_BLOCK;
@@ -595,7 +701,7 @@ bool sgnn_conv_epi_supported(int cin, int cout) {
 int sgnn_conv_fwd_impl(const float *x, int64_t n_in, int cin, const float *w, int K, const int32_t *table, int64_t ld,
                        int64_t n_out, int cout, float *y, int flags, int in_shift, const int32_t *kmap,
                        const int32_t *kadd, int in_mul, int groups, int table_rows, const ConvEpi *epi_in,
-                       sgnn_stream_t stream) {
+                       sgnn_stream_t stream, const ConvPre *pre) {
   SGNN_CHECK_ARG(cin >= 1 && cout >= 1 && K >= 1 && K <= 64 && n_out >= 0 && ld >= n_out && in_shift >= 0 &&
                  in_shift < 31 && in_mul >= 1 && groups >= 1 && groups <= 64 && table_rows >= 1 &&
                  table_rows <= 64 && (kmap || table_rows >= K));
@@ -642,7 +748,22 @@ int sgnn_conv_fwd_impl(const float *x, int64_t n_in, int cin, const float *w, in
       conv_launch_big<CI, CO, EXV>(grid4, s, x, n_in, w, table, ld, K, n_out, y, flags, in_shift, ex, epi); \
     done = true;                                                                                        \
   } while (0)
-  if (plain && !small && g_tune.conv_unrolled && sgnn_conv_u_supported(cin, cout, K))
+  if (pre) {   // folded BatchNormReLU in front of the gathers: the small-level kernel only (prog.hip plans it there)
+    SGNN_CHECK_ARG(plain && flags == 0 && in_shift == 0 && sgnn_conv_fold_small_ok(cin, cout, K, n_out));
+    SGNN_CHECK_ARG(pre->fuse.save_mean && pre->fuse.save_invstd && pre->n_bn > 0);
+    SGNN_CHECK_ARG(pre->fuse.partial ? (pre->fuse.nblk >= 1 && (((uintptr_t)pre->fuse.partial) & 15) == 0)
+                                     : (pre->fuse.running_mean && pre->fuse.running_var));
+#define X(CI, CO)                                                                                              \
+  if (!done && cin == CI && cout == CO) {                                                                      \
+    SGNN_LAUNCH((k_conv_small<CI, CO, ConvPre>), dim3((unsigned)((n_out + 15) / 16)), dim3(256), 0, s, x, n_in, w, \
+                table, ld, K, n_out, y, flags, in_shift, epi, *pre);                                           \
+    done = true;                                                                                               \
+  }
+    CONV_PRE_CASES(X)
+#undef X
+    SGNN_CHECK_ARG(done);
+  }
+  if (!done && plain && !small && g_tune.conv_unrolled && sgnn_conv_u_supported(cin, cout, K))
     done = sgnn_conv_u_launch(x, n_in, cin, w, K, table, ld, n_out, cout, y, flags, in_shift, epi, s);
 #define X(CI, CO) \
   if (!done && plain && cin == CI && cout == CO) LAUNCH_FWD(CI, CO, false);
@@ -799,12 +920,20 @@ struct DwCfg {
 #ifndef DW_PAIR
 #define DW_PAIR 1
 #endif
-template <int CIN, int COUT, bool EX, int KPBT = 0>
+// PRE (k_conv_dw<.., 1, DwPre>, the one-offset form of the small levels only): x holds the input rows of a folded BatchNormReLU
+// (see k_conv_small); the layer is applied to the gathered rows with the statistics the forward kernel stored.
+struct DwPre {
+  const float *mean, *invstd, *gamma, *beta;
+  float leak;
+};
+template <int CIN, int COUT, bool EX, int KPBT = 0, class... PREARG>
 __global__ __launch_bounds__(256) void k_conv_dw(const float *__restrict__ x, int64_t n_in,
                                                 const float *__restrict__ dy, const int32_t *__restrict__ table,
                                                 int64_t ld, int K, int64_t n_out, float *__restrict__ partial,
                                                 int64_t rows_per_block, int in_shift, ConvEx ex, int64_t ldx,
-                                                int64_t ld_dy, const int64_t *n_dev) {
+                                                int64_t ld_dy, const int64_t *n_dev, PREARG... prearg) {
+  constexpr bool PRE = sizeof...(PREARG) == 1;
+  static_assert(sizeof...(PREARG) <= 1, "at most one folded layer");
   if (n_dev) {   // capacity mode: spread the LIVE rows over all row blocks of the (capacity-sized) launch
     n_out = sgnn_dyn_n(n_out, n_dev);
     const int64_t per = (n_out + gridDim.x - 1) / gridDim.x;
@@ -888,6 +1017,31 @@ __global__ __launch_bounds__(256) void k_conv_dw(const float *__restrict__ x, in
 #pragma unroll
         for (int s = 0; s < GW; ++s)
           if (3 * V + s >= CIN) g[m][s] = (q == 3) ? 0.f : g[m][s];
+    }
+  };
+  // PRE: this lane's channels are GW consecutive ones from pch0 on, in either gather mapping
+  static_assert(!PRE || (KPBT == 1 && !EX && CINP == CIN), "folded BatchNorm: the one-offset kernel of whole quarters");
+  float pm[PRE ? GW : 1], pi[PRE ? GW : 1], pg[PRE ? GW : 1], pb[PRE ? GW : 1];
+  if constexpr (PRE) {
+    const DwPre &pre = conv_pack_first(prearg...);
+    const int pch0 = RCX ? rc_chunk * 4 : q * V;
+#pragma unroll
+    for (int s = 0; s < GW; ++s) {
+      pm[s] = pre.mean[pch0 + s];
+      pi[s] = pre.invstd[pch0 + s];
+      pg[s] = pre.gamma ? pre.gamma[pch0 + s] : 1.f;
+      pb[s] = pre.beta ? pre.beta[pch0 + s] : 0.f;
+    }
+  }
+  auto act_rows = [&](int32_t iv, float(&g)[NI][GW]) {   // rows of missing rules stay exact zeros
+    if constexpr (PRE) {
+      const float leak = conv_pack_first(prearg...).leak;
+#pragma unroll
+      for (int m = 0; m < NI; ++m) {
+        const int32_t id = __builtin_amdgcn_ds_bpermute((RCX ? m * RPI + rc_row : m * 16 + i16) * 4, iv);
+#pragma unroll
+        for (int s = 0; s < GW; ++s) g[m][s] = id < 0 ? 0.f : sgnn_bn_act(g[m][s], pm[s], pi[s], pg[s], pb[s], leak);
+      }
     }
   };
   auto store_rows = [&](const float(&g)[NI][GW]) {   // the wave's 64 gathered rows -> xs[row][CINP]
@@ -1027,6 +1181,7 @@ __global__ __launch_bounds__(256) void k_conv_dw(const float *__restrict__ x, in
         if (kk + 1 < DW_KPB) gather(idxv[kk + 1], g1);               // compile-time conditions only
         __builtin_amdgcn_sched_barrier(0);
         norm_rows(g0);
+        if constexpr (PRE) act_rows(idxv[kk], g0);
         store_rows(g0);
         mma_chunk(kk, b);
         __builtin_amdgcn_sched_barrier(0);
@@ -1034,6 +1189,7 @@ __global__ __launch_bounds__(256) void k_conv_dw(const float *__restrict__ x, in
           if (kk + 2 < DW_KPB) gather(idxv[kk + 2], g0);
           __builtin_amdgcn_sched_barrier(0);
           norm_rows(g1);
+          if constexpr (PRE) act_rows(idxv[kk + 1], g1);
           store_rows(g1);
           mma_chunk(kk + 1, b);
           __builtin_amdgcn_sched_barrier(0);
@@ -1260,7 +1416,6 @@ __global__ __launch_bounds__(256) void k_conv_dw_generic(const float *__restrict
   dw[e] = s;
 }
 
-#define DW_FINE_ROWS 16384   // below: one offset per weight-gradient workgroup
 static int64_t dw_rows_per_block(int64_t n_out) {
   int64_t rpb = (n_out + g_tune.conv_dw_blocks - 1) / g_tune.conv_dw_blocks;   // <= g_tune.conv_dw_blocks row blocks
   rpb = ((rpb + 255) / 256) * 256;             // whole 256-row wave rounds
@@ -1300,7 +1455,7 @@ SGNN_EXPORT int sgnn_conv_bwd_weight_ex(const float *x, int64_t n_in, int cin, c
 int sgnn_conv_bwd_weight_impl(const float *x, int64_t n_in, int cin, int64_t ldx, const float *dy, int cout, int64_t ld_dy,
                               const int32_t *table, int64_t ld, int K, int64_t n_out, float *dw, int in_shift,
                               const int32_t *kmap, const int32_t *kadd, int in_mul, int groups, int table_rows, void *ws,
-                              int64_t ws_bytes, sgnn_stream_t stream, const int64_t *n_dev) {
+                              int64_t ws_bytes, sgnn_stream_t stream, const int64_t *n_dev, const ConvPre *pre) {
   SGNN_CHECK_ARG(ldx >= cin && ldx <= 1024 && ld_dy >= cout && ld_dy <= 1024);
   SGNN_CHECK_ARG(cin >= 1 && cout >= 1 && K >= 1 && K <= 64 && n_out >= 0 && ld >= n_out && dw &&
                  in_shift >= 0 && in_shift < 31 && in_mul >= 1 && groups >= 1 && groups <= 64 && table_rows >= 1 &&
@@ -1355,7 +1510,31 @@ int sgnn_conv_bwd_weight_impl(const float *x, int64_t n_in, int cin, int64_t ldx
     }                                                                                                      \
     done = true;                                                                                           \
   } while (0)
-  if (plain && cin == 1 && cout == 8 && g_tune.conv_dw_c1) {   // one-channel input: the VALU kernel (k_conv_dw_c1)
+  if (pre) {   // folded BatchNormReLU in front of the gathers (statistics: what the forward kernel stored)
+    SGNN_CHECK_ARG(plain && in_shift == 0 && sgnn_conv_fold_small_ok(cin, cout, K, n_out) && pre->fuse.save_mean &&
+                   pre->fuse.save_invstd);
+    if (!ws || ws_bytes < sgnn_conv_bwd_weight_ws_bytes(n_out, K, cin, cout)) {
+      sgnn_set_error("sgnn_conv_bwd_weight: workspace too small");
+      return SGNN_ENOWS;
+    }
+    const DwPre dp{pre->fuse.save_mean, pre->fuse.save_invstd, pre->gamma, pre->beta, pre->leak};
+    const int prof = sgnn_prof_begin_launch(1, n_out, cin, cout, K, 0, s);
+#define X(CI, CO)                                                                                                    \
+  if (!done && cin == CI && cout == CO) {                                                                            \
+    SGNN_LAUNCH((k_conv_dw<CI, CO, false, 1, DwPre>), dim3((unsigned)nblk, (unsigned)K), dim3(256), 0, s, x, n_in, dy, table, ld, \
+                K, n_out, (float *)ws, rpb, in_shift, ex, ldx, ld_dy, n_dev, dp);                                    \
+    done = true;                                                                                                     \
+  }
+    CONV_PRE_CASES(X)
+#undef X
+    sgnn_prof_end_launch(prof, s);
+    SGNN_CHECK_ARG(done);
+    if (sgnn_dw_batch && sgnn_dw_batch->n < DW_BATCH_MAX)
+      sgnn_dw_batch->d[sgnn_dw_batch->n++] = DwDesc{(const float *)ws, dw, nblk, elems, 0};
+    else
+      SGNN_LAUNCH(k_dw_reduce, dim3((unsigned)((elems + 31) / 32)), dim3(256), 0, s, (const float *)ws, nblk, elems, dw);
+  }
+  if (!done && plain && cin == 1 && cout == 8 && g_tune.conv_dw_c1) {   // one-channel input: the VALU kernel (k_conv_dw_c1)
     if (!ws || ws_bytes < sgnn_conv_bwd_weight_ws_bytes(n_out, K, cin, cout)) {
       sgnn_set_error("sgnn_conv_bwd_weight: workspace too small");
       return SGNN_ENOWS;

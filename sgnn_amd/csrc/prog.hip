@@ -12,6 +12,7 @@
 #include <mutex>
 #include <vector>
 #include "common.h"
+#include "bn_fuse.h"
 
 enum {
   OP_CONV_SUBM = 0, OP_CONV_DOWN = 1, OP_UNPOOL = 2, OP_BN = 3, OP_ADD = 4, OP_JOIN = 5,
@@ -117,10 +118,13 @@ std::vector<int> count_readers(const View &v) {
 #define g_fuse (g_tune.prog_fusion != 0)
 #define g_lin_add (g_tune.prog_lin_add != 0)
 #define g_lin_bn (g_tune.prog_lin_bn != 0)
+#define g_bn_fold (g_tune.prog_bn_fold_small != 0)
 // What the executor decides once per call, identically in forward and backward:
 //  * add_dst[i] >= 0: convolution i writes straight into the output of the AddTable right behind it (fused add);
 //  * views: a JoinTable whose inputs can be produced in place gets no copy — its inputs LIVE in column ranges of the
-//    join buffer (root / col / ld), every producer writes and every consumer reads through a row stride.
+//    join buffer (root / col / ld), every producer writes and every consumer reads through a row stride;
+//  * fold[i] >= 0: BatchNormReLU i launches nothing — convolution fold[i], its only reader, applies it to the rows it
+//    gathers (forward and weight gradient; pre_bn[fold[i]] = i).  Small levels of the training layout only (plan_bn_folds).
 struct Plan {
   std::vector<int> add_dst;      // per op
   std::vector<int> add_src;      // per op: the other input of that AddTable, which the convolution adds while it stores
@@ -128,6 +132,7 @@ struct Plan {
   std::vector<int> root, col;    // per buffer: storage owner and column offset inside it
   std::vector<int64_t> ld;       // per buffer: row stride in floats
   std::vector<char> join_view;   // per op: this JoinTable is in place
+  std::vector<int> fold, pre_bn; // per op: BatchNorm -> the convolution that applies it; convolution -> the BatchNorm it applies (-1: none)
   std::vector<int> lin_bn;       // per op: a LINEAR head whose data gradient is formed inside the backward pass of BatchNorm lin_bn[i] (BnLin; -1: written)
   Kind kind = TRAINING;          // INFERENCE_BF16: ld in bf16 elements, a multiple of 8 (LINEAR outputs: fp32, ld = channels)
   std::vector<char> f32;         // per buffer: stored as fp32 (always, except in the bf16 layout where only LINEAR outputs are)
@@ -142,6 +147,65 @@ bool strided_conv_ok(const Op &o) {
   return sgnn_conv_epi_supported(o.cin, o.cout) && sgnn_conv_epi_supported(o.cout, o.cin) && dw_shape_ok(o.cin, o.cout);
 }
 
+// The convolution whose epilogue leaves the statistics partials of BatchNorm i in a training-mode forward pass (the
+// convolution right in front of it, or in front of the AddTable fused into it), -1: the BatchNorm runs its own statistics pass
+int stats_producer(const View &v, const Plan &P, int i) {
+  const Op &b = v.op(i);
+  for (int p = i - 1; p >= 0 && p >= i - 2; --p) {
+    const Op &o = v.op(p);
+    const bool fused_add = P.add_dst[p] >= 0;
+    if (p + 1 + (fused_add ? 1 : 0) != i || !o.is_conv()) continue;
+    if ((fused_add ? P.add_dst[p] : o.out) != b.in0) continue;
+    if (!sgnn_conv_epi_supported(o.cin, o.cout) || ConvSetup(v, o).n_out <= 0) continue;
+    return p;
+  }
+  return -1;
+}
+
+// BatchNorm i and the op right behind it have the shape of a fold (what can be told from the ops and the row counts alone)
+bool fold_candidate(const View &v, int i) {
+  if (i + 1 >= v.nops) return false;
+  const Op &b = v.op(i), &o = v.op(i + 1);
+  if (b.type != OP_BN || !o.is_conv() || o.in0 != b.out || o.lev != b.lev || o.cin != b.cin) return false;
+  const ConvSetup cs(v, o);
+  return cs.ok && sgnn_conv_fold_small_ok(o.cin, o.cout, cs.K, cs.n_out);
+}
+
+// BatchNormReLU folded into its only reader (sgnn_tune.prog_bn_fold_small).  On a small level the layer is one node of the
+// dependent chain — arguments, two rounds over the partial table, two barriers, rows in, rows out — whose output is gathered
+// once by the forward convolution and once by its weight gradient.  Folded, the convolution sums the table under its own rule
+// and gather loads and the node disappears.  Only where
+//  * the training layout is planned (the liveness-packed inference arenas keep the layer as a pass);
+//  * nothing but ONE convolution reads the output (no AddTable, JoinTable, head or caller), the output is no view, that
+//    convolution is the NEXT op (the layer's partial table lives in the shared statistics workspace: unfolded it is consumed
+//    right behind its producer, and folded it must be too, before another convolution's epilogue writes there), and it runs
+//    k_conv_small forward and k_conv_dw<.., 1> for its weight gradient (sgnn_conv_fold_small_ok);
+//  * the statistics partials come from a convolution epilogue and pass bn_fuse_ok with the CONSUMER's grid, and
+//    sgnn_tune.bn_fuse is on (the pass then sums the table in the same order: bit-identical statistics).
+// The same decision in training and eval mode (eval reads the running statistics; no table), forward and backward.
+// The backward pass needs no other change: k_bn_bwd_apply re-derives the ReLU mask from the BatchNorm input, the data
+// gradient reads dy, and the only other reader of the output — the weight gradient — applies the layer itself.
+void plan_bn_folds(const View &v, const std::vector<int> &readers, Plan &P) {
+  if (!g_bn_fold || !g_tune.bn_fuse || P.kind != TRAINING) return;
+  for (int i = 0; i < v.nops; ++i) {
+    const Op &b = v.op(i);
+    if (b.type != OP_BN || b.out < v.n_ext || b.out >= v.nbuf || readers[b.out] != 1 || P.root[b.out] != b.out) continue;
+    if (b.lev < 0 || b.lev >= v.nlev || v.lev_n[b.lev] <= 0) continue;
+    const int j = i + 1;
+    if (j >= v.nops || !fold_candidate(v, i)) continue;
+    const Op &o = v.op(j);
+    const ConvSetup cs(v, o);
+    if (!cs.ok || !sgnn_conv_fold_small_ok(o.cin, o.cout, cs.K, cs.n_out)) continue;
+    const int p = stats_producer(v, P, i);
+    if (p < 0) continue;
+    const Op &po = v.op(p);
+    const int64_t nblk = sgnn_conv_grid_blocks(ConvSetup(v, po).n_out, po.cin, po.cout, po.K());
+    if (!bn_fuse_ok(nblk, b.cin, (cs.n_out + 15) / 16)) continue;
+    P.fold[i] = j;
+    P.pre_bn[j] = i;
+  }
+}
+
 void make_plan(const View &v, const int32_t *keep, Plan &P, Kind kind) {
   P.kind = kind;
   P.f32.assign(v.nbuf, P.bf16() ? 0 : 1);
@@ -154,6 +218,8 @@ void make_plan(const View &v, const int32_t *keep, Plan &P, Kind kind) {
   P.skip.assign(v.nops, 0);
   P.join_view.assign(v.nops, 0);
   P.lin_bn.assign(v.nops, -1);
+  P.fold.assign(v.nops, -1);
+  P.pre_bn.assign(v.nops, -1);
   P.root.resize(v.nbuf);
   P.col.assign(v.nbuf, 0);
   P.ld.resize(v.nbuf);
@@ -243,6 +309,7 @@ void make_plan(const View &v, const int32_t *keep, Plan &P, Kind kind) {
     P.col[b] = c;
     P.ld[b] = row_ld(r);
   }
+  plan_bn_folds(v, readers, P);
 }
 
 // arena layout: [buffers (in-place JoinTable inputs own no storage)..., per-op areas (BatchNorm: mean/invstd;
@@ -456,7 +523,15 @@ int64_t ws_stats(const View &v) {
   return (need + 255) & ~int64_t(255);
 }
 
-int64_t ws_need(const View &v) { return ws_main(v) + ws_stats(v); }
+// a program that may fold a BatchNorm gets two tables: a convolution that sums the table of a folded BatchNorm in its prologue
+// writes its own partials into the other one (sized from the ops alone: the sizing entry point knows neither readers nor layout)
+bool may_fold(const View &v) {
+  if (!g_fuse || !g_bn_fold || !g_tune.bn_fuse) return false;
+  for (int i = 0; i + 1 < v.nops; ++i)
+    if (fold_candidate(v, i)) return true;
+  return false;
+}
+int64_t ws_need(const View &v) { return ws_main(v) + (may_fold(v) ? 2 : 1) * ws_stats(v); }
 
 // weight-gradient lane: sgnn_prog_backward can run every dW (+ its reduce) on a second stream with its own
 // workspace, concurrently with the dX / BatchNorm chain that forms the critical path (both only READ dy)
@@ -496,7 +571,7 @@ struct Ctx {
   // fp32 passes: the statistics partials a convolution epilogue has left for BatchNorm op i (pre[i], pre_nblk[i] blocks)
   std::vector<const double *> pre;
   std::vector<int64_t> pre_nblk;
-  double *stats_ws;
+  double *stats_ws, *stats_ws2;
 
   // plan and layout of these descriptors; false: they do not describe a program
   bool prepare(Kind kind, const int32_t *keep) {
@@ -505,6 +580,7 @@ struct Ctx {
     pre = std::vector<const double *>(v.nops, nullptr);
     pre_nblk = std::vector<int64_t>(v.nops, 0);
     stats_ws = (double *)((char *)ws + ws_main(v));
+    stats_ws2 = (double *)((char *)stats_ws + ws_stats(v));
     return true;
   }
   int ch(int b) const { return b < 0 ? 0 : v.bufs[2 * b + 1]; }
@@ -517,6 +593,27 @@ struct Ctx {
   const int64_t *count(int c) const { return (lev_cnt && c >= 0 && c < v.nlev) ? (const int64_t *)lev_cnt[c] : nullptr; }
   // the stride-2 tables and everything of the coarser levels (hash, 3x3x3 rulebooks, row counts) may still be in
   // flight on the caller's pyramid lane: the first Convolution(2,2) is the first operation that touches them
+  // BatchNorm op i as the convolution it is folded into applies it; save: the layer's mean / invstd area
+  ConvPre conv_pre(int i, float *save, bool forward) const {
+    const Op &b = v.op(i);
+    ConvPre p{};
+    if (forward && training) {
+      p.fuse.partial = pre[i];
+      p.fuse.nblk = (int)pre_nblk[i];
+    }
+    p.fuse.eps = v.opf[4 * i];
+    p.fuse.momentum = v.opf[4 * i + 1];
+    p.fuse.running_mean = param(b.par + 2);
+    p.fuse.running_var = param(b.par + 3);
+    p.fuse.save_mean = save;
+    p.fuse.save_invstd = save + b.cin;
+    p.gamma = param(b.par);
+    p.beta = param(b.par + 1);
+    p.leak = v.opf[4 * i + 2];
+    p.n_bn = v.lev_n[b.lev];
+    p.n_bn_dev = count(b.lev);
+    return p;
+  }
   int wait_once(void *&wait_event) const {
     if (!wait_event) return SGNN_OK;
     sgnn_stamp("down-wait<", stream);
@@ -767,13 +864,27 @@ SGNN_EXPORT int sgnn_prog_forward(const int32_t *ops, const float *opf, int nops
         if (g_fuse && training && cs.n_out > 0 && j < nops && v.op(j).type == OP_BN && v.op(j).in0 == dst_buf &&
             sgnn_conv_epi_supported(cin, cout)) {
           epi.stats = 1;
-          epi.partial = c.stats_ws;
-          c.pre[j] = c.stats_ws;
+          // (a folded BatchNorm's table is read by every workgroup of this launch while the others store their partials)
+          epi.partial = (PL.pre_bn[i] >= 0 && c.pre[PL.pre_bn[i]] == c.stats_ws) ? c.stats_ws2 : c.stats_ws;
+          c.pre[j] = epi.partial;
           c.pre_nblk[j] = sgnn_conv_grid_blocks(cs.n_out, cin, cout, cs.K);
         }
-        epi.ldx = c.ld(in0);
         epi.ldy = c.ld(dst_buf);
         epi.n_dev = c.count(cs.cnt_class);
+        if (PL.pre_bn[i] >= 0) {             // the BatchNormReLU in front of it was not run: its INPUT rows are gathered
+          const int bi = PL.pre_bn[i];
+          const ConvPre cp = c.conv_pre(bi, arena + L.aux_off[bi], true);
+          if (training && !cp.fuse.partial) {
+            sgnn_set_error("sgnn_prog_forward: a folded BatchNorm has no statistics partials");
+            return SGNN_EINVAL;
+          }
+          const int bin = v.op(bi).in0;
+          epi.ldx = c.ld(bin);
+          PROG_TRY(sgnn_conv_fwd_impl(B(bin), n, cin, c.param(par), cs.K, cs.tab_f, cs.ld_f, cs.n_out, cout, B(dst_buf), 0, 0,
+                                      nullptr, nullptr, 1, 1, cs.K, &epi, stream, &cp));
+          break;
+        }
+        epi.ldx = c.ld(in0);
         PROG_TRY(sgnn_conv_fwd_impl(B(in0), n, cin, c.param(par), cs.K, cs.tab_f, cs.ld_f, cs.n_out, cout, B(dst_buf), 0, 0,
                                     nullptr, nullptr, 1, 1, cs.K, &epi, stream));
         break;
@@ -784,6 +895,7 @@ SGNN_EXPORT int sgnn_prog_forward(const int32_t *ops, const float *opf, int nops
                                      c.count(lev)));
         break;
       case OP_BN: {
+        if (PL.fold[i] >= 0) break;          // convolution fold[i] applies the layer (and stores its statistics)
         float *save = arena + L.aux_off[i];
         PROG_TRY(sgnn_bn_fwd_impl(B(in0), c.ld(in0), n, cin, c.param(par), c.param(par + 1), c.param(par + 2), c.param(par + 3),
                                   opf[4 * i], opf[4 * i + 1], training, opf[4 * i + 2], save, save + cin, B(out), c.ld(out),
@@ -1032,9 +1144,17 @@ int bwd_conv(Ctx &c, Grads &g, Lane &lane, int i) {
     }
   }
   const int64_t slice = dw_slice(c.v, i);
-  PROG_TRY(sgnn_conv_bwd_weight_impl(g.X(in0), cs.n, cin, c.ld(in0), dy, cout, ld_dy, cs.tab_f, cs.ld_f, cs.K, cs.n_out,
-                                     g.PG(o.par), 0, nullptr, nullptr, 1, 1, cs.K, lane.ws + lane.off, slice, (sgnn_stream_t)ls,
-                                     c.count(cs.cnt_class)));
+  if (c.P.pre_bn[i] >= 0) {   // in0 was never stored: the weight gradient applies the folded BatchNormReLU to that layer's input
+    const int bi = c.P.pre_bn[i], bin = c.v.op(bi).in0;
+    const ConvPre cp = c.conv_pre(bi, const_cast<float *>(g.arena) + c.L.aux_off[bi], false);
+    PROG_TRY(sgnn_conv_bwd_weight_impl(g.X(bin), cs.n, cin, c.ld(bin), dy, cout, ld_dy, cs.tab_f, cs.ld_f, cs.K, cs.n_out,
+                                       g.PG(o.par), 0, nullptr, nullptr, 1, 1, cs.K, lane.ws + lane.off, slice, (sgnn_stream_t)ls,
+                                       c.count(cs.cnt_class), &cp));
+  } else {
+    PROG_TRY(sgnn_conv_bwd_weight_impl(g.X(in0), cs.n, cin, c.ld(in0), dy, cout, ld_dy, cs.tab_f, cs.ld_f, cs.K, cs.n_out,
+                                       g.PG(o.par), 0, nullptr, nullptr, 1, 1, cs.K, lane.ws + lane.off, slice, (sgnn_stream_t)ls,
+                                       c.count(cs.cnt_class)));
+  }
   if (ls != lane.hs) sgnn_stamp("dw>", (sgnn_stream_t)ls);      // (nothing unless stamps are on: scripts/lane_stamps.py)
   lane.off += slice;
   return SGNN_OK;

@@ -20,6 +20,7 @@ sgnn_tune g_tune = {
     /* prog_lin_bn         */ 1,
     /* prog_lin_add        */ 1,
     /* bn_fuse             */ 1,
+    /* prog_bn_fold_small  */ 1,
 };
 
 namespace {
@@ -44,6 +45,7 @@ const Field kFields[] = {
     {"prog_lin_bn", &sgnn_tune::prog_lin_bn, 0, 1, true},
     {"prog_lin_add", &sgnn_tune::prog_lin_add, 0, 1, true},
     {"bn_fuse", &sgnn_tune::bn_fuse, 0, 1, true},
+    {"prog_bn_fold_small", &sgnn_tune::prog_bn_fold_small, 0, 1, true},
 };
 const Field *find(const char *name) {
   if (!name) return nullptr;

@@ -1174,6 +1174,59 @@ int sgnn_simp_place(const float *verts, int nverts, const int32_t *faces, int nt
                     uint8_t *out_colors, sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Mesh fairing (sgnn_amd.smooth; rules in INTEGRATION.md section Y).  Topology never changes: every stage reads faces
+ * (ntri,3) i32 and rows of 3 floats and writes new rows.  A face with a repeated index contributes nothing anywhere; a
+ * face with an index outside [0, nverts) is not dereferenced and raises SGNN_STATUS_COORD_RANGE in *status.
+ * The adjacency, chained by the caller:
+ *   sgnn_smooth_keys      -> keys (6 * ntri) i64: (a << 32 | b) for both directions of the three edges of every face,
+ *                            2^63 - 1 six times for a face that contributes nothing
+ *   (caller: sort the keys)
+ *   sgnn_smooth_run_flags -> flags[j] u8 = 1 where sorted key j is a real key and differs from key j - 1
+ *   (caller: sel = sgnn_compact_mask(flags), nruns = its count)
+ *   sgnn_smooth_runs      -> source[r], neighbor[r] i32 = the two halves of the key of run r, mult[r] u8 = the length of
+ *                            the run, clamped to 255: the number of faces on the undirected edge
+ *   (caller: start (nverts + 1) i64 = exclusive scan of the counts of source)
+ *   sgnn_smooth_classify  -> kind[i] u8: 0 no edge, 3 an edge of multiplicity above 2, else 2 an edge of multiplicity
+ *                            1, else 1
+ * One umbrella step:
+ *   sgnn_smooth_step      -> xout = xin + f * (mean of the used neighbours - xin) for every vertex that moves, xin
+ *                            elsewhere; rows of `stride` floats (3, or 4 on 16-byte boundaries with the fourth written
+ *                            as 0); mode 0 'fixed', 1 'curve', 2 'free' for kind 2; fixed (nverts) u8 or NULL; status
+ *                            non-NULL: a non-finite coordinate of xin raises SGNN_STATUS_COORD_RANGE.  xin != xout.
+ * Normals.  order (3 * ntri) i64 is the stable sort of the corner keys by vertex and cstart (nverts + 2) i64 the
+ * exclusive scan of their counts (list nverts holds the corners of the faces that contribute nothing):
+ *   sgnn_smooth_face_normals   -> out (ntri,3): (b - a) x (c - a), divided by its length if unit (0 where that is 0);
+ *                                 status may be NULL
+ *   sgnn_smooth_corners        -> ckeys[3t + k] = faces[t][k], or nverts for a face that contributes nothing
+ *   sgnn_smooth_vertex_normals -> out (nverts,3): the unit sum of raw (ntri,3) over the faces of every vertex's list
+ * Denoising:
+ *   sgnn_smooth_filter    -> nout (ntri,3): one pass of the face-normal filter over nin, nin != nout
+ *   sgnn_smooth_update    -> xout (nverts,3): one pass of the vertex update towards the planes of the filtered
+ *                            normals; kind, fixed and status as in sgnn_smooth_step
+ * One lane per vertex or face sums its list in order; no floating-point atomics: the same input gives the same bits.
+ * nverts < 2^31, 6 * ntri < 2^31.
+ * ------------------------------------------------------------------------- */
+int sgnn_smooth_keys(const int32_t *faces, int ntri, int nverts, int64_t *keys, int32_t *status, sgnn_stream_t stream);
+int sgnn_smooth_run_flags(const int64_t *keys, int64_t n, uint8_t *flags, sgnn_stream_t stream);
+int sgnn_smooth_runs(const int64_t *keys, int64_t n, const int32_t *sel, int64_t nruns, int32_t *source,
+                     int32_t *neighbor, uint8_t *mult, sgnn_stream_t stream);
+int sgnn_smooth_classify(const int64_t *start, const uint8_t *mult, int nverts, uint8_t *kind, sgnn_stream_t stream);
+int sgnn_smooth_step(const float *xin, float *xout, int nverts, int stride, const int64_t *start,
+                     const int32_t *neighbor, const uint8_t *mult, const uint8_t *kind, const uint8_t *fixed, int mode,
+                     float f, int32_t *status, sgnn_stream_t stream);
+int sgnn_smooth_face_normals(const float *verts, int nverts, const int32_t *faces, int ntri, int unit, float *out,
+                             int32_t *status, sgnn_stream_t stream);
+int sgnn_smooth_corners(const int32_t *faces, int ntri, int nverts, int32_t *ckeys, int32_t *status,
+                        sgnn_stream_t stream);
+int sgnn_smooth_vertex_normals(const float *raw, int ntri, const int64_t *order, const int64_t *cstart, int nverts,
+                               float *out, sgnn_stream_t stream);
+int sgnn_smooth_filter(const float *nin, float *nout, const int32_t *faces, int ntri, int nverts, const int64_t *order,
+                       const int64_t *cstart, float threshold, sgnn_stream_t stream);
+int sgnn_smooth_update(const float *xin, float *xout, int nverts, const int32_t *faces, int ntri, const float *normals,
+                       const int64_t *order, const int64_t *cstart, const uint8_t *kind, const uint8_t *fixed,
+                       int32_t *status, sgnn_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Triangle meshes to signed distance volumes (sgnn_amd.voxelize; rules in INTEGRATION.md section L).  The mesh is in
  * grid coordinates (voxel (i, j, k) has its centre at the integer point); records, boxes and usable come from
  * sgnn_meshdist_pack.  Volumes are (dz, dy, dx), x fastest, every dimension in [1, 65535] and fewer than 2^31 voxels;

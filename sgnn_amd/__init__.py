@@ -12,6 +12,7 @@ Package contents (only what the hot path of SURVEY.md §8 needs):
   register.py  point sets and volumes registered against a TSDF volume: transforms for regrid.merge (section R)
   upright.py   the gravity-aligned room frame of a scan volume: the transform for regrid.grid_for (section S)
   sensor.py    a depth sensor simulated on rendered frames: noise, disparity steps, shadow, ragged edges (section V)
+  smooth.py    triangle meshes faired: adjacency, Laplacian / Taubin smoothing, normals, denoising (section Y)
   raytrace.py  arbitrary rays against a triangle mesh: closest hits, scanner sweeps for points, visibility (section W)
 """
 __version__ = '0.1.0'

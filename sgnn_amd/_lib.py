@@ -190,6 +190,16 @@ PROTOTYPES = {
     'sgnn_simp_mark': (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp]),
     'sgnn_simp_place': (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_i32,
                                 c_vp, c_vp, c_vp]),
+    'sgnn_smooth_keys': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    'sgnn_smooth_run_flags': (c_i32, [c_vp, c_i64, c_vp, c_vp]),
+    'sgnn_smooth_runs': (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    'sgnn_smooth_classify': (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp]),
+    'sgnn_smooth_step': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_f32, c_vp, c_vp]),
+    'sgnn_smooth_face_normals': (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    'sgnn_smooth_corners': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    'sgnn_smooth_vertex_normals': (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    'sgnn_smooth_filter': (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp]),
+    'sgnn_smooth_update': (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'sgnn_vox_grid_coords': (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     'sgnn_vox_bricks_count': (c_i32, [c_vp, c_i32, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'sgnn_vox_bricks_fill': (c_i32, [c_vp, c_i32, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),

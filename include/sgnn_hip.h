@@ -1227,6 +1227,63 @@ int sgnn_smooth_update(const float *xin, float *xout, int nverts, const int32_t 
                        int32_t *status, sgnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Point-cloud neighbourhoods (sgnn_amd.cloud; rules in INTEGRATION.md section Z).  Points and queries are rows of 3
+ * floats; a row with a non-finite coordinate is never a neighbour and gets the empty answer as a query.  The grid is
+ * (lox, loy, loz, cell, nx, ny, nz): at most 1024 cells an axis and fewer than 2^31 - 1 in all, x fastest; the cell of
+ * a coordinate is floor((p - lo) / cell) in fp32, clamped to the grid.  No answer depends on the grid.
+ * The index, chained by the caller:
+ *   sgnn_cloud_keys   -> keys[i] i64 = (cell << 32 | i), cell 2^31 - 1 for a non-finite row (points and queries alike)
+ *   (caller: sort the keys; nfin = the number of finite rows)
+ *   sgnn_cloud_pack   -> packed (nfin,4) f32 on a 16-byte boundary: (x, y, z, bits of the index) in key order, and
+ *                        start (ncell + 1) i32: the first record of every cell
+ * Queries.  qkeys are the sorted keys of the queries; queries == NULL takes the indexed points themselves as queries
+ * (nq = nfin, qkeys unused), each without its own row, and writes to row `index` of nrows:
+ *   sgnn_cloud_knn          -> idx (nrows,k) i32 and d2 (nrows,k) f32: the first k of (d2, index) with d2 <= limit2,
+ *                              -1 and +inf where there are fewer; k in [1, 32]; d2 = (dx*dx + dy*dy) + dz*dz in fp32
+ *   sgnn_cloud_radius_count -> count[q] i32 = the points with d2 <= limit2
+ *   sgnn_cloud_radius_fill  -> out[qstart[q] + .] i64 = (q << 32 | index) of those points in no order, qstart
+ *                              (nq + 1) i64 the exclusive scan of count (the caller sorts out)
+ * Consumers of the rows of sgnn_cloud_knn over the points themselves:
+ *   sgnn_cloud_normals   -> normal (n,3) f32, variation (n) f32, valid (n) u8 by fp64 covariance and five cyclic Jacobi
+ *                           sweeps; toward_mode 0 none (toward NULL), 1 one viewpoint (3 floats), 2 one per point (n,3)
+ *   sgnn_cloud_mean_dist -> mean (n) f64: the mean of the fp32 roots of the row, +inf for an empty row
+ * Voxel down-sampling on the world lattice:
+ *   sgnn_cloud_voxel_keys   -> keys[i] i64: 21 bits an axis (z, y, x from the top) of floor(p / cell) + 2^20 - 1, 2^63 - 1
+ *                              for a non-finite row and for a cell at or beyond +-2^20, which also raises
+ *                              SGNN_STATUS_COORD_RANGE in *status
+ *   (caller: stable sort -> keys, order)
+ *   sgnn_cloud_run_flags    -> flags[j] u8 = 1 where sorted key j is a real key and differs from key j - 1
+ *   (caller: sel = sgnn_compact_mask(flags), nruns = its count, nvalid = the number of real keys)
+ *   sgnn_cloud_voxel_reduce -> per run: mean position (fp64 sum in member order / count), rounded colour means (ncol 3
+ *                              or 4, or 0 with colors NULL), unit sum of normals (or NULL), count, first member, and
+ *                              cell_of[member] = run
+ * No floating-point atomics: the same input gives the same bits.  Every count is below 2^31.
+ * ------------------------------------------------------------------------- */
+int sgnn_cloud_keys(const float *points, int64_t n, float lox, float loy, float loz, float cell, int nx, int ny, int nz,
+                    int64_t *keys, sgnn_stream_t stream);
+int sgnn_cloud_pack(const float *points, int64_t n, const int64_t *keys, int64_t nfin, int64_t ncell, float *packed,
+                    int32_t *start, sgnn_stream_t stream);
+int sgnn_cloud_knn(const float *packed, int64_t nfin, const int32_t *start, float lox, float loy, float loz, float cell,
+                   int nx, int ny, int nz, const float *queries, const int64_t *qkeys, int64_t nq, int64_t nrows, int k,
+                   float limit2, int32_t *idx, float *d2, sgnn_stream_t stream);
+int sgnn_cloud_radius_count(const float *packed, int64_t nfin, const int32_t *start, float lox, float loy, float loz,
+                            float cell, int nx, int ny, int nz, const float *queries, const int64_t *qkeys, int64_t nq,
+                            float limit2, int32_t *count, sgnn_stream_t stream);
+int sgnn_cloud_radius_fill(const float *packed, int64_t nfin, const int32_t *start, float lox, float loy, float loz,
+                           float cell, int nx, int ny, int nz, const float *queries, const int64_t *qkeys, int64_t nq,
+                           float limit2, const int64_t *qstart, int64_t *out, sgnn_stream_t stream);
+int sgnn_cloud_normals(const float *points, int64_t n, const int32_t *nbr, int k, const float *toward, int toward_mode,
+                       float *normal, float *variation, uint8_t *valid, sgnn_stream_t stream);
+int sgnn_cloud_mean_dist(const int32_t *nbr, const float *d2, int64_t n, int k, double *mean, sgnn_stream_t stream);
+int sgnn_cloud_voxel_keys(const float *points, int64_t n, float cell, int64_t *keys, int32_t *status,
+                          sgnn_stream_t stream);
+int sgnn_cloud_run_flags(const int64_t *keys, int64_t n, uint8_t *flags, sgnn_stream_t stream);
+int sgnn_cloud_voxel_reduce(const float *points, int64_t n, const uint8_t *colors, int ncol, const float *normals,
+                            const int64_t *order, const int32_t *sel, int64_t nruns, int64_t nvalid, float *out_points,
+                            uint8_t *out_colors, float *out_normals, int32_t *count, int32_t *first, int32_t *cell_of,
+                            sgnn_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Triangle meshes to signed distance volumes (sgnn_amd.voxelize; rules in INTEGRATION.md section L).  The mesh is in
  * grid coordinates (voxel (i, j, k) has its centre at the integer point); records, boxes and usable come from
  * sgnn_meshdist_pack.  Volumes are (dz, dy, dx), x fastest, every dimension in [1, 65535] and fewer than 2^31 voxels;

@@ -14,6 +14,7 @@ Package contents (only what the hot path of SURVEY.md §8 needs):
   sensor.py    a depth sensor simulated on rendered frames: noise, disparity steps, shadow, ragged edges (section V)
   smooth.py    triangle meshes faired: adjacency, Laplacian / Taubin smoothing, normals, denoising (section Y)
   raytrace.py  arbitrary rays against a triangle mesh: closest hits, scanner sweeps for points, visibility (section W)
+  cloud.py     point-cloud neighbourhoods: exact kNN and radius search, normals, outlier filters, voxel thinning (section Z)
 """
 __version__ = '0.1.0'
 
@@ -24,7 +25,7 @@ def __getattr__(name):
     if name == 'bf16_inference':
         from .scn.program import bf16_inference
         return bf16_inference
-    if name in ('track', 'register', 'upright', 'sensor', 'raytrace'):   # sgnn_amd.track / .register / .upright / .sensor / .raytrace without an import statement of their own, as lazily as the above
+    if name in ('track', 'register', 'upright', 'sensor', 'raytrace', 'cloud'):   # sgnn_amd.track / .register / .upright / .sensor / .raytrace / .cloud without an import statement of their own, as lazily as the above
         import importlib
         return importlib.import_module('.' + name, __name__)
     raise AttributeError(name)

@@ -200,6 +200,20 @@ PROTOTYPES = {
     'sgnn_smooth_vertex_normals': (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
     'sgnn_smooth_filter': (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp]),
     'sgnn_smooth_update': (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'sgnn_cloud_keys': (c_i32, [c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    'sgnn_cloud_pack': (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    'sgnn_cloud_knn': (c_i32, [c_vp, c_i64, c_vp, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_i64,
+                               c_i32, c_f32, c_vp, c_vp, c_vp]),
+    'sgnn_cloud_radius_count': (c_i32, [c_vp, c_i64, c_vp, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp,
+                                        c_i64, c_f32, c_vp, c_vp]),
+    'sgnn_cloud_radius_fill': (c_i32, [c_vp, c_i64, c_vp, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp,
+                                       c_i64, c_f32, c_vp, c_vp, c_vp]),
+    'sgnn_cloud_normals': (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    'sgnn_cloud_mean_dist': (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
+    'sgnn_cloud_voxel_keys': (c_i32, [c_vp, c_i64, c_f32, c_vp, c_vp, c_vp]),
+    'sgnn_cloud_run_flags': (c_i32, [c_vp, c_i64, c_vp, c_vp]),
+    'sgnn_cloud_voxel_reduce': (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                        c_vp, c_vp, c_vp]),
     'sgnn_vox_grid_coords': (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     'sgnn_vox_bricks_count': (c_i32, [c_vp, c_i32, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'sgnn_vox_bricks_fill': (c_i32, [c_vp, c_i32, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
